@@ -7,20 +7,21 @@ image patched by deltas) -> `_raw.out`, `_assembled_reads.fa`, `_final.out`), pr
 text, device bring-up and every host phase are INSIDE the timed region (the boundary hands over files, as run-trust4:508 does,
 so there is no "inputs resident in HBM" variant of this metric; the kernel-only numbers are in `roofline` / `passes`).
 
-N = 1. The workload is BASELINE.json's config C2 ITSELF (1 M synthetic 150 bp PE pairs, 20 k clones, seed 1, -f hg38_bcrtcr.fa,
-bulk mode) whenever `steps + warmup` runs of it fit into the time the WHOLE run of bench.py may take (T4_BENCH_BUDGET_S, default 1770 s from
-process start to the printed line: the driver stops bench.py after 1800 s, and its 20 + 5 steps of C2 at 58-61 s per step need
-1450-1525 s of that; decided from the first run's own seconds and what has been spent by then): the first run is C2 in
-any case -- it is compared with the committed md5 sums of the reference's outputs, it is the first warm-up step when C2 is the
-workload, and it is reported as `c2` (with its own roofline block and a same-box reference timing on a stated prefix of the same
-files). When the runs do not fit, the steps are timed on the C2 recipe at 100 k pairs (`config.workload` says which ran).
+N = 1. The workload is the C2 recipe of BASELINE.json (synthetic 150 bp PE pairs, pairs / 50 clones, seed 1, -f hg38_bcrtcr.fa,
+bulk mode) at `--pairs` pairs (default 100 k), or with `--c2 1` config C2 ITSELF (1 M pairs, 20 k clones): the workload follows from
+the arguments alone, so the same arguments time the same inputs on every run, and exactly `--steps` steps are timed (`ms_per_step`
+is one of them). With `--c2 1` the first run of C2 is the first warm-up step -- it is compared with the committed md5 sums of the
+reference's outputs and reported as `c2` (with its own roofline block and, with --cpu-baseline 1, a same-box reference timing on a
+stated prefix of the same files). `--dump-outputs DIR` writes what the last timed step computed as float arrays (dump_outputs).
 Rank 0 also reports
-  cpu_baseline   the reference binary (oracle/_ref/trust4) on the SAME box: on the whole batch of the timed steps when that is the
-                 100 k-pair batch (outputs compared byte for byte, `parity_on_bench_batch`), on the first 100 k pairs of C2's files
-                 when C2 is the workload (-t <host cores>; `sample` names the files);
+  cpu_baseline   with --cpu-baseline 1, the reference binary (oracle/_ref/trust4, when it travelled) on the SAME box: on the whole
+                 batch of the timed steps when that is the --pairs batch (outputs compared byte for byte, `parity_on_bench_batch`), on the first 100 k pairs of
+                 C2's files when C2 is the workload (-t <host cores>; `sample` names the files);
   roofline       the dominant kernels of a step (the AddRead query launches), HIP-event time on the engine's stream, bytes as
-                 SURVEY 8d defines them, `traffic` from two rocprofv3 PMC passes of the 100 k-pair command;
-  passes         kernel-level numbers of the two GPU passes and the rough-annotation pass alone over a resident C2 batch;
+                 SURVEY 8d defines them, with --traffic 1 `traffic` from two rocprofv3 PMC passes of the 100 k-pair command;
+  passes         kernel-level numbers of the two GPU passes: the AddRead queries of the step, and the rough-annotation pass alone
+                 through the engine in this process over the batch's reads resident in HBM (with --side-legs 1 also over a C2-sized batch);
+and, with --side-legs 1, while the run stays inside `--budget` (T4_BENCH_BUDGET_S, default 1770 s from process start):
   stage1_cells   whole stage 1 in barcode mode (C5 recipe sample) next to the reference binary;
   stage1_cells_1m  the same at 1 M pairs / 10 k cells (-t 32), files against the digests of the reference's run on that sample;
   stage0_e2e     the stage-0 candidate filter next to the reference binary.
@@ -140,8 +141,8 @@ def cpu_baseline(tmp, fa, f1, f2, pairs, mine_prefix, single_prefix_pairs):
     return out, same
 
 
-def annotate_pass_c2(device, pairs, clones, steps):
-    """The data-parallel pass alone over a resident C2-sized batch: stage-1 rough annotation of every read
+def annotate_pass(device, pairs, clones, steps):
+    """The data-parallel pass alone, through the engine in this process (trust4_amd -> libt4hip.so), over a resident batch of the C2 recipe: stage-1 rough annotation of every read
     (main.cpp:1084-1120), inputs 2-bit packed in HBM before the timed region, results left on the device."""
     import t4libs
     import trust4_amd
@@ -163,7 +164,7 @@ def annotate_pass_c2(device, pairs, clones, steps):
     dt = time.perf_counter() - t0
     k_ms = float(np.mean(kms))
     alg = annotate_bytes(n_reads, 150, hits)
-    return {"workload": "C2: %d pairs (%d reads), %d clones, seed 1; rough annotation of every read, inputs resident, results on the device" % (pairs, n_reads, clones),
+    return {"workload": "C2 recipe: %d pairs (%d reads), %d clones, seed 1; rough annotation of every read, inputs resident, results on the device" % (pairs, n_reads, clones),
             "reads_per_s": n_reads * steps / dt, "ms_per_pass": dt / steps * 1e3, "kernel_ms": k_ms, "hits_per_read": hits / n_reads,
             "tier_reads": eng.stats()["tier_reads"],
             "roofline": {"bound": "hbm", "achieved": alg / (k_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -178,6 +179,105 @@ def file_md5(path):
         for blk in iter(lambda: f.read(1 << 22), b""):
             h.update(blk)
     return h.hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20240601
+BASE_CODE = np.full(256, 4, dtype=np.float32)   # consensus characters as numbers: A 0, C 1, G 2, T 3, anything else 4
+BASE_CODE[[ord(c) for c in "ACGT"]] = [0, 1, 2, 3]
+
+
+def _records(path):
+    """(header, body lines) of every '>' record of a stage-1 output file, in file order"""
+    head, body = None, []
+    with open(path) as f:
+        for line in f:
+            line = line.rstrip("\n")
+            if line.startswith(">"):
+                if head is not None:
+                    yield head, body
+                head, body = line, []
+            elif head is not None:
+                body.append(line)
+    if head is not None:
+        yield head, body
+
+
+def _crc(head, body):
+    import zlib
+    return zlib.crc32(("\n".join([head] + body) + "\n").encode())
+
+
+def _sample(n, cap):
+    """indices of a fixed, seeded sample of n rows (all of them when n <= cap), in file order"""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+
+
+def dump_outputs(prefix, out_dir):
+    """What one stage 1 hands its caller -- the contigs of `_final.out` (consensus and per-position A/C/G/T weights, main.cpp's
+    output format) and the reads of `_assembled_reads.fa` -- as float arrays in out_dir/<name>.npy, at most DUMP_LIMIT_BYTES in all:
+      totals               [contigs, consensus positions, reads, bytes of _raw.out, _final.out, _assembled_reads.fa]
+      contig_{index,length,crc32}   per contig of a seeded sample of at most 512 k contigs (crc32 of its whole record, header included)
+      raw_contig_crc32     the same for `_raw.out` (the contigs before the mate-pair extension tail)
+      contig_consensus / contig_posweight   consensus codes (A 0, C 1, G 2, T 3, other 4) and the 4 x L weights of a seeded sample
+                           of contigs in file order, 1 M positions at most; contig_posweight_index names those contigs
+      read_{index,length,crc32,fields}  per read of a seeded sample of at most 512 k reads: its length, crc32 of its record and the
+                           numbers of its header after the name (NaN where a field is not a number)
+    The sample is the same for every run with the same number of records, so two builds of the project compare array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    contigs = list(_records(prefix + "_final.out"))
+    for head, body in contigs:
+        if len(body) != 5 or any(len(row.split()) != len(body[0]) for row in body[1:]):
+            raise SystemExit("dump_outputs: %s: a contig record that is not a consensus line and four weight rows (%s)" % (prefix + "_final.out", head[:80]))
+    ci = _sample(len(contigs), 512 << 10)
+    arrays["contig_index"] = ci.astype(np.float64)
+    arrays["contig_length"] = np.array([len(contigs[i][1][0]) for i in ci], dtype=np.float64)
+    arrays["contig_crc32"] = np.array([_crc(*contigs[i]) for i in ci], dtype=np.float64)
+    raw = list(_records(prefix + "_raw.out"))
+    arrays["raw_contig_crc32"] = np.array([_crc(*raw[i]) for i in _sample(len(raw), 512 << 10)], dtype=np.float64)
+    pw_idx, left = [], 1 << 20
+    for i in np.random.default_rng(DUMP_SEED).permutation(len(contigs)):
+        if len(contigs[i][1][0]) <= left:
+            pw_idx.append(int(i))
+            left -= len(contigs[i][1][0])
+    pw_idx.sort()
+    arrays["contig_posweight_index"] = np.array(pw_idx, dtype=np.float64)
+    arrays["contig_consensus"] = np.concatenate([BASE_CODE[np.frombuffer(contigs[i][1][0].encode(), dtype=np.uint8)] for i in pw_idx] or [np.zeros(0, np.float32)])
+    arrays["contig_posweight"] = np.concatenate([np.array([row.split() for row in contigs[i][1][1:]], dtype=np.float32).reshape(4, -1) for i in pw_idx] or [np.zeros((4, 0), np.float32)], axis=1)
+    n_contigs, n_pos = len(contigs), sum(len(b[0]) for _, b in contigs)
+    del contigs, raw
+    n_reads = sum(1 for _ in _records(prefix + "_assembled_reads.fa"))
+    ri = _sample(n_reads, 512 << 10)
+    keep = np.zeros(n_reads, dtype=bool)
+    keep[ri] = True
+    lengths, crcs, fields = [], [], []
+    for j, (head, body) in enumerate(_records(prefix + "_assembled_reads.fa")):
+        if keep[j]:
+            lengths.append(sum(len(x) for x in body))
+            crcs.append(_crc(head, body))
+            vals = []
+            for tok in head.split()[1:]:
+                try:
+                    vals.append(float(int(tok)))
+                except ValueError:
+                    vals.append(float("nan"))
+            fields.append(vals)
+    width = max([len(v) for v in fields] or [0])
+    arrays["read_index"] = ri.astype(np.float64)
+    arrays["read_length"] = np.array(lengths, dtype=np.float32)
+    arrays["read_crc32"] = np.array(crcs, dtype=np.float64)
+    arrays["read_fields"] = np.array([v + [float("nan")] * (width - len(v)) for v in fields], dtype=np.float32).reshape(len(fields), width)
+    arrays["totals"] = np.array([n_contigs, n_pos, n_reads] +
+                                [os.path.getsize(prefix + x) for x in ("_raw.out", "_final.out", "_assembled_reads.fa")], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("dump_outputs: %d bytes of arrays, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def add_roofline(aq, note=""):
@@ -575,6 +675,8 @@ def sharded_cells(args, rank, local_rank, world, dist):
         except OSError:
             line["config"]["transport"] = None
         md5s = {x: file_md5(out + x) for x in OUT_SUFFIXES}
+        if args.dump_outputs:
+            dump_outputs(out, args.dump_outputs)
         one = os.path.join(tmp, "one_rank")
         t1 = time.perf_counter()
         p = subprocess.run([driver, "-t", str(threads)] + argv + ["-o", one], env=dict(os.environ, T4_DEVICE="0" if dry else str(local_rank)), stderr=subprocess.PIPE, text=True)
@@ -596,25 +698,26 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--pairs", type=int, default=0, help="read pairs per step: 0 = config C2 itself (1 M pairs) when steps + warmup runs of it fit the budget, else the C2 recipe at 100 k pairs; "
-                                                         "a number forces the C2 recipe at that size")
-    ap.add_argument("--fallback-pairs", type=int, default=100000, help="pairs of the C2-recipe batch the steps are timed on when C2 itself does not fit")
+    ap.add_argument("--pairs", type=int, default=100000, help="read pairs per step: the C2 recipe (SURVEY 8d: seed 1, pairs / 50 clones) at this size")
     ap.add_argument("--clones", type=int, default=0, help="clones of the batch (default: pairs / 50, the C2 ratio)")
     ap.add_argument("--threads", type=int, default=8, help="host threads of trust4-hip (-t)")
     ap.add_argument("--budget", type=float, default=float(os.environ.get("T4_BENCH_BUDGET_S", "1770")),
                     help="seconds the WHOLE run may take, process start to the printed line (the driver stops bench.py after 1800 s): decides whether C2 itself is the workload and which side legs run")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="0 = skip the reference legs")
+    ap.add_argument("--cpu-baseline", type=int, default=0, help="1 = also time the reference binary (oracle/_ref/trust4, when it travelled) on the same files")
     ap.add_argument("--cpu-single-pairs", type=int, default=20000, help="prefix timed with the reference's -t 1 (0 = skip)")
     ap.add_argument("--cpu-c2-pairs", type=int, default=100000, help="prefix of C2's files the reference is timed on, on this box (0 = skip)")
-    ap.add_argument("--side-legs", type=int, default=1, help="0 = skip passes.rough_annotation_c2 / stage1_cells / stage0_e2e")
-    ap.add_argument("--traffic", type=int, default=1, help="0 = skip the two rocprofv3 PMC passes that measure roofline.traffic")
-    ap.add_argument("--c2", type=int, default=1, help="0 = skip the run of config C2 itself (then the steps are timed on the 100 k-pair batch)")
+    ap.add_argument("--side-legs", type=int, default=0, help="1 = also run passes.rough_annotation_c2 / stage1_cells / stage0_e2e / stage1_cells_1m and --config-leg (while the budget lasts)")
+    ap.add_argument("--traffic", type=int, default=0, help="1 = also run the two rocprofv3 PMC passes that measure roofline.traffic (while the budget lasts)")
+    ap.add_argument("--c2", type=int, default=0, help="1 = time config C2 itself (1 M pairs, about 50 s per step) instead of the --pairs batch: its first run is the first warm-up step, its outputs are checked against the reference's digests")
     ap.add_argument("--config-leg", default="", help="additional config legs, comma separated (c3p05, c3p2, c3p5: prefixes of C3; c5m5 / c5m20: the C5 recipe at 5 M / 20 M pairs over 50 k cells, barcode mode; c2:dropin = C2 with default options through the reference's main.cpp bound to the C ABI)")
     ap.add_argument("--cells-pairs", type=int, default=250000, help="N > 1: pairs of the barcode-mode sample per GPU of the job")
     ap.add_argument("--cells", type=int, default=2500, help="N > 1: cells of the sample per GPU of the job")
     ap.add_argument("--cells-total", type=int, default=0, help="N > 1: cells of the whole sample instead of --cells per GPU (fewer cells than ranks: ranks without a cell)")
     ap.add_argument("--cells-threads", type=int, default=16, help="N > 1: host threads per rank")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.pairs < 1:
+        raise SystemExit("--steps and --pairs must be at least 1 and --warmup at least 0")
 
     import torch
     import trust4_amd.build
@@ -661,27 +764,30 @@ def main():
         def spent():
             return time.time() - T_PROC0
         c2 = None
-        use_c2 = False
         c2_cpu = None
         c2name = "c2"
-        if args.pairs == 0 and args.c2:
-            # config C2 itself, once: digest check, the first warm-up step if C2 is the workload, the `c2` record either way
+        # the workload follows from the arguments alone, so that the same arguments time the same inputs on every run: the C2 recipe
+        # at --pairs pairs, or with --c2 1 config C2 itself, whose first run is the first warm-up step
+        use_c2 = bool(args.c2)
+        if use_c2:
+            # config C2 itself, once: digest check, the first warm-up step, the `c2` record
             c2dir = os.path.join(tmp, "c2")
             os.makedirs(c2dir)
             c2name = os.environ.get("T4_BENCH_C2_STANDIN", "c2")   # testing aid: "c2mini" walks the same code in seconds (the line then says it is not config C2)
             c2 = config_leg(c2name, threads, local_rank, keep=c2dir)
-            # the reference on this box on a prefix of C2's own files, BEFORE the steps: the line carries its cpu_baseline whatever the
-            # steps leave of the budget (about 30 s; nothing else runs beside it or beside a timed step)
-            if "files" in c2 and args.cpu_baseline and os.path.exists(REF_BIN) and args.cpu_c2_pairs > 0:
+            if "seconds" not in c2:
+                raise SystemExit("bench.py: the run of config %s failed: %s" % (c2name.upper(), c2.get("error", c2)))
+            # the reference on this box on a prefix of C2's own files, BEFORE the steps (about 30 s; nothing else runs beside it or beside a timed step)
+            if args.cpu_baseline and os.path.exists(REF_BIN) and args.cpu_c2_pairs > 0:
                 try:
                     c2_cpu = config_leg_cpu_only(c2["files"], c2name, min(args.cpu_c2_pairs, c2["pairs"]), limit_s=max(30.0, min(300.0, args.budget - spent() - 200)))
                 except Exception as e:   # noqa: BLE001
                     c2_cpu = {"value": None, "unit": "pairs/s", "cores": host_cores(), "kind": "reference", "sample": "not measured: %s" % repr(e)[:200]}
-            # C2 is the workload when the remaining steps + warm-up runs of it (1.5 % slack; runs of one box differ by less), and 20 s for what
-            # must follow them (md5 sums of the outputs, the line), end inside the budget
-            need = c2.get("seconds", 1e9) * (args.steps + args.warmup - 1) * 1.015 + 20
-            use_c2 = "seconds" in c2 and args.warmup >= 1 and spent() + need <= args.budget
-            c2["workload_decision"] = {"spent_s_before_the_steps": spent(), "needed_s": need, "budget_s": args.budget}
+            # what the remaining warm-up runs and the steps will take (1.5 % slack) and 20 s for what must follow them: the optional legs
+            # (--side-legs, --traffic) only run before the steps while the budget leaves room for them; the steps themselves always run
+            need = c2["seconds"] * max(0, args.steps + args.warmup - 1) * 1.015 + 20
+            c2["workload_decision"] = {"spent_s_before_the_steps": spent(), "needed_s": need, "budget_s": args.budget,
+                                       "rule": "config C2 with --c2 1, else the --pairs batch; the budget decides the optional legs only"}
 
         def pmc_on_small_batch(limit_s):
             """roofline.traffic when C2 is the workload: the two PMC passes run on the C2 recipe at 100 k pairs (a C2 run under the
@@ -705,7 +811,7 @@ def main():
                 c2["workload_decision"]["pmc_passes_before_the_steps_s"] = spent() - c2["workload_decision"]["spent_s_before_the_steps"]
             except Exception as e:   # noqa: BLE001
                 pmc_early = (None, {"error": repr(e)[:300]}, None)
-        pairs = c2["pairs"] if use_c2 else (args.pairs if args.pairs > 0 else args.fallback_pairs)
+        pairs = c2["pairs"] if use_c2 else args.pairs
         clones = args.clones if args.clones > 0 else max(1, pairs // 50)
         if use_c2:
             fa, f1, f2, _, _ = c2["files"]
@@ -718,17 +824,12 @@ def main():
             run_stage1(fa, f1, f2, mine, threads, local_rank)
         sync()
         t0 = time.perf_counter()
-        steps_done = 0
         for _ in range(args.steps):
-            # last resort, never expected (the decision above leaves slack): a box that turned so much slower during the steps that the
-            # next one would run into the driver's limit -- a line over the steps that were timed, saying so, instead of no line at all
-            if use_c2 and steps_done >= 1 and spent() + (time.perf_counter() - t0) / steps_done * 1.03 > args.budget + 15:
-                break
             run_stage1(fa, f1, f2, mine, threads, local_rank, stats=stats_path)
-            steps_done += 1
         sync()
         dt = time.perf_counter() - t0
-        steps_asked, args.steps = args.steps, steps_done
+        if args.dump_outputs:
+            dump_outputs(mine, args.dump_outputs)
 
         st = json.load(open(stats_path))
         ph = st["phases_s"]
@@ -736,9 +837,7 @@ def main():
         alg_ann = annotate_bytes(ra["reads"], 150, ra["hits"])
         roof = add_roofline(aq)
         workload = (("config C2 itself: 1000000 synthetic 150 bp PE pairs (20000 clones, seed 1)" if c2name == "c2" else "NOT config C2 -- the stand-in %s of T4_BENCH_C2_STANDIN: %d pairs (%d clones, seed 1)" % (c2name, pairs, clones)) if use_c2 else
-                    "C2 recipe, %d synthetic 150 bp PE pairs (%d clones, seed 1)%s" % (pairs, clones,
-                    ": config C2 itself takes %.1f s per step here, %d steps + %d warm-up do not fit the budget of %.0f s -- C2 is the `c2` record of this line"
-                    % (c2["seconds"], args.steps, args.warmup, args.budget) if c2 and "seconds" in c2 else ""))
+                    "C2 recipe, %d synthetic 150 bp PE pairs (%d clones, seed 1)" % (pairs, clones))
         out = {
             "metric": "stage-1 assembly read pairs/sec (150 bp PE), whole stage 1",
             "value": pairs * args.steps / dt,
@@ -759,8 +858,8 @@ def main():
                        "rough_annotation_in_step": {"reads": ra["reads"], "hits": ra["hits"], "kernel_ms": ra["kernel_ms"],
                                                     "achieved_GBs": alg_ann / (max(ra["kernel_ms"], 1e-6) * 1e-3) / 1e9}},
         }
-        if steps_done != steps_asked:
-            out["steps_cut_short"] = "%d of the %d steps asked for were timed: the next one would have ended beyond the %d s the whole run may take" % (steps_done, steps_asked, int(args.budget))
+        if not dry:   # the kernel-level number of the data-parallel pass: the rough annotation alone over this batch's reads, resident in HBM
+            out["passes"]["rough_annotation_resident"] = annotate_pass(local_rank, pairs, clones, 3)
         if use_c2:
             out["parity_on_bench_batch"] = bool(c2.get("identical")) and all(file_md5(mine + x) == c2["md5"][x] for x in OUT_SUFFIXES)
         # the reference on this box
@@ -769,8 +868,6 @@ def main():
                 out["cpu_baseline"] = c2_cpu
             else:
                 out["cpu_baseline"], out["parity_on_bench_batch"] = cpu_baseline(tmp, fa, f1, f2, pairs, mine, args.cpu_single_pairs)
-                if c2 and c2_cpu:
-                    c2["cpu_baseline"] = c2_cpu
         left = args.budget + 10 - spent()   # what follows is left out when it could run into the driver's limit
         if args.traffic and pmc_early is None and left < 150:
             out["roofline"]["traffic_detail"] = {"skipped": "%.0f s left of the run's budget: the two PMC passes are in the line of `python bench.py` with its default steps (profiles/)" % left}
@@ -821,7 +918,7 @@ def main():
             left = args.budget + 10 - spent()   # side legs only while the whole run stays inside the driver's limit
             if left > 300:
                 try:
-                    out["passes"]["rough_annotation_c2"] = annotate_pass_c2(local_rank, 1000000, 20000, 3)
+                    out["passes"]["rough_annotation_c2"] = annotate_pass(local_rank, 1000000, 20000, 3)
                 except Exception as e:   # noqa: BLE001
                     out["passes"]["rough_annotation_c2"] = {"error": repr(e)[:300]}
                 out["stage1_cells"] = stage1_cells(100000, 1000)

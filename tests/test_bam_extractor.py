@@ -1,5 +1,5 @@
 """bam-extractor-hip (stage 0 for BAM input) against the reference's bam-extractor binary (oracle/_ref, built from BamExtractor.cpp
-and the BAM library of its vendored samtools): the repo's example.bam where the reference tree exists, and synthetic BAM files
+and the BAM library of its vendored samtools): the reference's example.bam against that binary's stored outputs, and synthetic BAM files
 written here (BGZF + BAM records by hand) that walk every branch -- reads inside V/J/C genes and their mates, unaligned templates,
 reads on alternative contigs, one-end-unaligned pairs, secondary records, reverse-strand records, spliced / clipped CIGARs,
 low-complexity reads, barcode and UMI tags behind tags of other types; paired and single-end. Outputs byte for byte."""
@@ -194,11 +194,19 @@ def test_bam_extractor_synthetic_emulated(tmp_path):
     synthetic_cases(tmp_path, emulated_bam_extractor(), 60)
 
 
-@needs_ref
-@pytest.mark.skipif(not os.path.exists("/root/reference/example/example.bam"), reason="the reference tree (example.bam) is not here")
 def test_bam_extractor_example_emulated(tmp_path):
-    kept = compare(tmp_path, emulated_bam_extractor(), "/root/reference/example/example.bam", "/root/reference/hg38_bcrtcr.fa", [], True, False)
-    assert kept == 198
+    """the reference's example.bam (tests/golden/example.bam) against the reference bam-extractor's outputs on it, stored beside it
+    (tests/golden/example_bam_extracted_{1,2}.fq.gz: oracle/_ref/bam-extractor -t 1 -b example.bam -f data/hg38_bcrtcr.fa)"""
+    golden = os.path.join(ROOT, "tests", "golden")
+    fa = str(tmp_path / "ref.fa")
+    with gzip.open(REF_FA, "rb") as f, open(fa, "wb") as g:
+        shutil.copyfileobj(f, g)
+    my_o = str(tmp_path / "mine")
+    subprocess.run([emulated_bam_extractor(), "-b", os.path.join(golden, "example.bam"), "-f", fa, "-o", my_o], check=True, stderr=subprocess.DEVNULL)
+    for s in ("_1.fq", "_2.fq"):
+        with gzip.open(os.path.join(golden, "example_bam_extracted%s.gz" % s), "rb") as f:
+            assert open(my_o + s, "rb").read() == f.read(), s
+    assert sum(1 for _ in open(my_o + "_1.fq")) // 4 == 198
 
 
 def test_bam_extractor_refuses_damaged_records(tmp_path):

@@ -433,20 +433,47 @@ def _bench_single_dry_run(tmp_path, extra):
 
 def test_bench_single_gpu_workload_choice_dry_run(tmp_path):
     """`python bench.py --steps K --warmup W` at N = 1 without a GPU (T4_BENCH_CPU_DRYRUN: the emulated driver, a 400-pair stand-in for
-    config C2): the run of "C2" comes first, the reference's timing on a prefix of its files before the steps, then the choice of the
-    workload from what the WHOLE run may take -- inside the budget the steps are timed on the "C2" files (and the line says whether
-    that was config C2: here it was not), outside it on the fallback batch with the "C2" run as the `c2` record."""
+    config C2): with --c2 1 the run of "C2" comes first, the reference's timing on a prefix of its files before the steps, then the steps
+    on the "C2" files (and the line says whether that was config C2: here it was not) -- whatever the budget, which only decides the
+    optional legs; without it the steps are timed on the --pairs batch, next to the reference on that whole batch."""
     if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "trust4")):
         pytest.skip("oracle/_ref/trust4 not built")
-    line = _bench_single_dry_run(tmp_path, [])
+    line = _bench_single_dry_run(tmp_path, ["--c2", "1", "--cpu-baseline", "1"])
     assert line["steps"] == 1 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["value"] > 0 and line["scaling"] is None
     assert line["config"]["pairs_per_step"] == 400 and line["config"]["is_baseline_config_c2"] is False and "stand-in c2micro" in line["config"]["workload"]
     assert line["cpu_baseline"]["kind"] == "reference" and line["cpu_baseline"]["value"] > 0 and "first 200 pairs" in line["cpu_baseline"]["sample"]
     assert line["c2"]["workload_decision"]["budget_s"] == 1770 and line["c2"]["workload_decision"]["spent_s_before_the_steps"] > 0
     assert "steps_cut_short" not in line and line["roofline"]["traffic"] is None
-    # the whole run may take 1 s: "C2" cannot be the workload
-    line = _bench_single_dry_run(tmp_path, ["--budget", "1", "--fallback-pairs", "300"])
+    # the whole run may take 1 s: the workload stays the one the arguments name
+    line = _bench_single_dry_run(tmp_path, ["--c2", "1", "--cpu-baseline", "1", "--budget", "1", "--pairs", "300"])
+    assert line["steps"] == 1 and line["config"]["pairs_per_step"] == 400 and "stand-in c2micro" in line["config"]["workload"]
+    assert line["c2"]["pairs"] == 400 and line["cpu_baseline"]["value"] > 0 and "first 200 pairs" in line["cpu_baseline"]["sample"]
+    # without the run of "C2": the --pairs batch, the reference on all of it, outputs compared
+    line = _bench_single_dry_run(tmp_path, ["--cpu-baseline", "1", "--pairs", "300"])
     assert line["steps"] == 1 and line["config"]["pairs_per_step"] == 300 and line["config"]["is_baseline_config_c2"] is False
-    assert "do not fit the budget" in line["config"]["workload"]
     assert line["parity_on_bench_batch"] is True and line["cpu_baseline"]["value"] > 0 and "whole batch" in line["cpu_baseline"]["sample"]
-    assert line["c2"]["pairs"] == 400 and line["c2"]["cpu_baseline"]["value"] > 0
+    assert "c2" not in line
+
+
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """`--dump-outputs DIR` on the default path (the --pairs batch, no reference legs): the arrays of the last timed step (float32 /
+    float64, at most 64 MB), the same from run to run with the same workload; `--steps` is the number of timed steps and `ms_per_step`
+    the time of one."""
+    import numpy as np
+    lines, dumps = [], []
+    for tag, sw in (("a", ["--steps", "2", "--warmup", "0"]), ("b", ["--steps", "3", "--warmup", "2"])):
+        d = tmp_path / ("dump_" + tag)
+        line = _bench_single_dry_run(tmp_path, ["--pairs", "400", "--dump-outputs", str(d)] + sw)
+        lines.append(line)
+        dumps.append({f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+    assert [x["steps"] for x in lines] == [2, 3] and [x["warmup"] for x in lines] == [0, 2]
+    assert all(x["ms_per_step"] > 0 and abs(x["ms_per_step"] * x["steps"] * x["value"] / 1e3 - 400 * x["steps"]) < 1e-6 * 400 * x["steps"] for x in lines)
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"totals", "contig_posweight", "contig_consensus", "read_crc32", "read_fields"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
+    n_contigs, n_pos, n_reads = a["totals"][:3]
+    assert n_contigs > 0 and n_reads > 0 and a["contig_posweight"].shape == (4, n_pos) and a["contig_consensus"].shape == (n_pos,)
+    assert a["contig_posweight"].sum() > 0 and set(np.unique(a["contig_consensus"])) <= {0, 1, 2, 3, 4}

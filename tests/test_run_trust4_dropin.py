@@ -3,8 +3,9 @@ reference binaries, once with `trust4` and `fastq-extractor` replaced by this re
 be byte-identical (stage-0 candidates, stage-1 contigs, and everything the reference's annotator and report scripts derive from them).
 
 `run-trust4` finds its programs next to itself, so each run gets a scratch directory holding a copy of the script (made at test
-time, from /root/reference, into tmp -- nothing of the reference enters the repo), links to the reference's perl report scripts
-and links named `trust4` / `fastq-extractor` / `annotator` that point at the binaries under test. Needs /root/reference and perl:
+time, from the copies staged in oracle/_ref/pipeline, into tmp -- nothing of the reference enters the repo), links to the reference's
+perl report scripts and links named `trust4` / `fastq-extractor` / `annotator` that point at the binaries under test. Needs
+oracle/_ref (the emulated drop-in also the reference's main.cpp, from which it is built) and perl:
 it runs in the development container (emulator build of the kernels, CPU) and, with `-m gpu`, against the hipcc build where the
 reference tree exists."""
 import filecmp
@@ -19,15 +20,14 @@ import t4libs
 from t4libs import REF_FA, ROOT
 
 REF_BIN = os.path.join(ROOT, "oracle", "_ref")
-# the reference's driver script, report scripts, IMGT file and example reads: from the reference tree where it exists (this
-# container), else from the copies integration/make_dropin.py staged next to the checker binaries (git-ignored oracle/_ref/pipeline,
-# which travels to the GPU box)
-REF_TREE = "/root/reference" if os.path.exists("/root/reference/run-trust4") else os.path.join(REF_BIN, "pipeline")
+# the reference's driver script, report scripts, IMGT file and example reads: the copies integration/make_dropin.py staged next to
+# the checker binaries (git-ignored oracle/_ref/pipeline, which travels to the GPU box)
+REF_TREE = os.path.join(REF_BIN, "pipeline")
 DROPIN = os.path.join(REF_BIN, "trust4-dropin")
 needs_reference = pytest.mark.skipif(
     not (os.path.exists(os.path.join(REF_TREE, "run-trust4")) and shutil.which("perl")
          and all(os.path.exists(os.path.join(REF_BIN, b)) for b in ("trust4", "fastq-extractor", "annotator"))),
-    reason="needs run-trust4 + report scripts (/root/reference or oracle/_ref/pipeline), perl and oracle/_ref/{trust4,fastq-extractor,annotator}")
+    reason="needs run-trust4 + report scripts (oracle/_ref/pipeline), perl and oracle/_ref/{trust4,fastq-extractor,annotator}")
 
 
 def install_dir(path, trust4_bin, extractor_bin, bam_extractor_bin=None):
