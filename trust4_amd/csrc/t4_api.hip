@@ -71,7 +71,7 @@ struct AqCall {
   unsigned char *tierHint = nullptr;
   std::vector<unsigned char> allGlobal;
   size_t oPk, oNm, oLen, oBc, oSt, oLs, oVw, oFa, oOnly, oForce, oCs, oWide, oWideA, inBytes, pCb, pCc, pS8, pCnt, pSta, pNext, pNext2, pBase, pTick, pStab, pAux, pN4, pTail, pWctl, pWplan, pWstat, pWctlA, pWplanA, pWstatA, outBytes;
-  bool hasOnly = false, hasForce = false, wantCands = false, useMarks = false;
+  bool hasOnly = false, hasForce = false, wantCands = false;
   bool extendLater = false, wide = false, onlyRestricted = false;
   bool lazyDone = false, lazyStage = false;   // the wide pipeline behind the query kernel is launched only once the kernel is known to have deferred a read (aqEnd)
   int wideSafety = 32;   // of sixteenths: partitions are planned for half of their capacity
@@ -133,13 +133,11 @@ struct t4_ctx {
   // testing aids of the AddRead query path, read from the environment once per ctx (a query round is a few hundred microseconds; a
   // dozen getenv calls in it are not nothing)
   struct AqEnv {
-    bool forceGlobal, wideNoHint, wideEager;
-    int capLimit, extendDefer, poolCap, candCap, wideMinHits, wideSample;
+    bool forceGlobal;
+    int capLimit, extendDefer, poolCap, candCap, wideMinHits;
     AqEnv() {
       auto num = [](const char *n, int d) { const char *e = getenv(n); return e ? atoi(e) : d; };
-      forceGlobal = getenv("T4_AQ_FORCE_GLOBAL") != nullptr; wideNoHint = getenv("T4_WIDE_NO_HINT") != nullptr;
-      wideSample = num("T4_WIDE_SAMPLE", 256);   // hits sampled per planned partition for the partition boundaries of a wide read (0: 4 096 per read, the rule until round 6 -- a read that plans four partitions does not need them: kernels of C2 23.9 -> 23.3 s, no partition overflowed, profiles/r06g)
-      wideEager = getenv("T4_WIDE_EAGER") != nullptr;   // A/B aid: the five wide kernels behind every whole-query round's query kernel, as until round 6
+      forceGlobal = getenv("T4_AQ_FORCE_GLOBAL") != nullptr;
       capLimit = num("T4_AQ_CAP_LIMIT", 0); poolCap = num("T4_AQ_POOL_CAP", 0); candCap = num("T4_AQ_CAND_CAP", 1 << 18);
       // (64 until round 5: with light rounds extendKernel runs behind the whole-query rounds anyway, and a read's 17th overlap is better
       // off there -- profiles/r05e, r05f)
@@ -155,7 +153,7 @@ struct t4_ctx {
   int64_t wideCalls = 0, wideCallsDeferred = 0, wideCallsDirect = 0;   // calls with the wide query on; those whose query kernel deferred a read; those with reads on the second stream
   int wideSafetyKeep = 32, wideCallsSinceRepeat = 0;   // partition load factor that recent calls needed (of sixteenths: 32 = partitions planned half full); decays back when nothing overflows
   int64_t wideFlagCounts[6] = {0, 0, 0, 0, 0, 0};     // calls repeated because: reads, partitions, keys of a partition, overlaps of a partition, dependency records, other
-  int wideRecentParts = 0, wideRecentReads = 0;   // the largest counts of the last calls, decayed: sizes the (persistent) grids of the next call's wide kernels
+  int wideRecentParts = 0;   // the largest partition counts of the last calls, decayed: sizes the (persistent) grids of the next call's second-stream wide kernels
   double aqKernelMs = 0;    // HIP-event time of the query kernels of all AddRead query calls (per call: first launch .. last kernel)
   int64_t aqHits = 0;       // _hit records their seed stages emitted (H of SURVEY 8d)
 };
@@ -1700,7 +1698,7 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   q.oVw = al8(q.oLs + sizeof(int) * (size_t)n); q.oFa = al8(q.oVw + sizeof(int) * (size_t)n); q.oOnly = al8(q.oFa + sizeof(double) * (size_t)n);
   q.oForce = al8(q.oOnly + sizeof(int) * (size_t)n);
   q.oCs = al8(q.oForce + sizeof(int) * (size_t)n);
-  q.oWide = al8(q.oCs + sizeof(T4CandArgs)); q.hasOnly = onlySeq != nullptr; q.hasForce = forceMin != nullptr; q.wantCands = (wantCands & 1) != 0; q.useMarks = (wantCands & 2) != 0;
+  q.oWide = al8(q.oCs + sizeof(T4CandArgs)); q.hasOnly = onlySeq != nullptr; q.hasForce = forceMin != nullptr; q.wantCands = (wantCands & 1) != 0;
   q.oWideA = al8(q.oWide + sizeof(T4Wide)); q.inBytes = al8(q.oWideA + sizeof(T4Wide));
   q.pCnt = 0; q.pSta = al8(q.pCnt + sizeof(int) * (size_t)n); q.pNext = al8(q.pSta + sizeof(int) * (size_t)n);
   q.pNext2 = al8(q.pNext + sizeof(int) * (size_t)n); q.pBase = al8(q.pNext2 + sizeof(int) * (size_t)n);
@@ -1766,7 +1764,7 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   const bool forceGlobal = c->aqEnv.forceGlobal;   // testing aid: every read on the global-scratch tier
   if (forceGlobal && !smallFirst) { q.allGlobal.assign((size_t)n, 1); q.tierHint = tierHint = q.allGlobal.data(); q.wide = false; }
   // (with the wide query on, a hinted read -- served wide the last time -- starts on the second stream: wideSeedKernel)
-  auto direct = [&](int i) { return tierHint && tierHint[i] && !smallFirst && !(onlySeq && onlySeq[i] >= 0) && !(q.wide && c->aqEnv.wideNoHint); };
+  auto direct = [&](int i) { return tierHint && tierHint[i] && !smallFirst && !(onlySeq && onlySeq[i] >= 0); };
   int nFirst = 0, nDirect = 0;
   for (int i = 0; i < n; ++i) if (!direct(i)) ls[nFirst++] = i;
   for (int i = 0; i < n; ++i) if (direct(i)) ls[nFirst + nDirect++] = i;
@@ -1777,9 +1775,9 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   return r;
 }
 
-// the wide query of the reads the round's query kernel deferred, on the ctx's stream. known: the header of the call is on the host
-// (the counts of deferred reads and their partitions size the grids); else the grids are sized from what recent calls needed
-void aqLaunchDeferredWide(t4_ctx *c, bool known) {
+// the wide query of the reads the round's query kernel deferred, on the ctx's stream, once the header of the call is on the host
+// (the counts of deferred reads and their partitions size the grids)
+void aqLaunchDeferredWide(t4_ctx *c) {
   AqCall &q = c->aq;
   T4Wide w;
   memcpy(&w, c->aqInHost + q.oWide, sizeof w);
@@ -1787,9 +1785,8 @@ void aqLaunchDeferredWide(t4_ctx *c, bool known) {
   // The grids are persistent (any size serves any number of reads / partitions); an empty grid of several hundred 100 KB-LDS workgroups
   // still takes microseconds to come and go.
   auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; };
-  int parts = 2 * c->wideRecentParts + 4, reads = 2 * c->wideRecentReads + 2;
-  if (known) { const int *ctl = (const int *)(c->aqOutHost + q.pWctl); parts = ctl[1] + 1; reads = ctl[0]; }
-  const int gParts = clampi(parts, 4, cus * 2), gReads = clampi(reads, known ? 1 : 2, cus < 64 ? cus : 64);
+  const int *ctl = (const int *)(c->aqOutHost + q.pWctl);
+  const int gParts = clampi(ctl[1] + 1, 4, cus * 2), gReads = clampi(ctl[0], 1, cus < 64 ? cus : 64);
   hipLaunchKernelGGL(t4k::wideScatterKernel, dim3(clampi(8 * gParts, 16, cus * 8)), dim3(256), 0, c->stream, q.base, w);   // (a partition is planned for four of the kernel's chunks)
   hipLaunchKernelGGL((t4k::wideSortKernel<8192>), dim3(gParts), dim3(512), 0, c->stream, q.base, w);
   hipLaunchKernelGGL(t4k::wideStatsKernel, dim3(gReads), dim3(512), 0, c->stream, q.base, w);
@@ -1835,7 +1832,7 @@ int aqLaunch(t4_ctx *c) {
   if (q.wide) {
     if ((r = ensureWide(c, n, 1, 1))) return r;
     T4Wide w = wideHalf(c, 0), wa = wideHalf(c, 1);
-    w.enabled = 1; w.safetyNum = q.wideSafety; w.samplePerPart = wa.samplePerPart = c->aqEnv.wideSample;
+    w.enabled = 1; w.safetyNum = q.wideSafety;
     // Reads of up to T4_WIDE_MIN_HITS emitted hits stay with one workgroup (LDS tier, then its slice of global scratch inside the same
     // launch, beside the other reads of the round): the wide query's kernels run behind the launch and cost a round about 0.25 ms
     // whatever the read is (profiles/r04b-h); from the LDS tier.s capacity on it beats one workgroup.s global scratch (C2 122 -> 93 s, profiles/r04h_*). The testing aid T4_AQ_CAP_LIMIT lowers
@@ -1852,7 +1849,6 @@ int aqLaunch(t4_ctx *c) {
     memset(&cs, 0, sizeof cs);
     cs.stats8 = (int *)(c->aqOut + q.pS8);
     if (q.hasForce) cs.forceMin = (const int *)(c->aqIn + q.oForce);
-    cs.useMarks = q.useMarks ? 1 : 0;
     if (q.wantCands) {
       cs.candOut = c->candPoolDev; cs.candCap = c->candCap; cs.candCursor = (unsigned *)(c->aqOut + q.pTail + 32); cs.candOverflow = (int *)(c->aqOut + q.pTail + 36);
       cs.candBase = (int *)(c->aqOut + q.pCb); cs.candCnt = (int *)(c->aqOut + q.pCc);
@@ -1975,7 +1971,6 @@ int aqLaunch(t4_ctx *c) {
     // The reads the launch above deferred. Since round 5 a fresh heavy read is recognised on the host a round ahead and starts on the
     // second stream, so the query kernel defers a read in one whole-query round of twenty (config C2: 2 434 of 42 654): the five kernels
     // behind it were five empty grids in the others. They are launched when the header says that a read was deferred (aqEnd).
-    if (c->aqEnv.wideEager) { aqLaunchDeferredWide(c, false); HIPCHK(c, hipGetLastError()); q.lazyDone = true; }
     if (nDirect > 0) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evG, 0));   // the other pipeline's records are in the pool before the extensions run
   }
   if (extendLater) {   // all records of the batch, spread over the chip
@@ -2050,7 +2045,7 @@ int aqEnd(t4_ctx *c, AqResult *res) {
         const int recsBefore = (int)*(const unsigned *)(c->aqOutHost + pTail + 24);
         q.lazyStage = true;
         HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-        aqLaunchDeferredWide(c, true);
+        aqLaunchDeferredWide(c);
         HIPCHK(c, hipGetLastError());
         if (q.extendLater) {
           hipLaunchKernelGGL(t4k::extendKernel, dim3(c->cus * 16), dim3(64), 0, c->stream, q.base, bv, qa, recsBefore < c->aqPoolCap ? recsBefore : c->aqPoolCap);
@@ -2138,7 +2133,6 @@ int aqEnd(t4_ctx *c, AqResult *res) {
       ++c->wideCalls; if (ctl[0] > 0) ++c->wideCallsDeferred; if (ctlA[0] > 0) ++c->wideCallsDirect;
       if (ctl[0] + ctlA[0] > 0 && ++c->wideCallsSinceRepeat >= 2048 && c->wideSafetyKeep > 32) { c->wideSafetyKeep /= 2; c->wideCallsSinceRepeat = 0; }
       c->wideRecentParts = ctl[1] > c->wideRecentParts ? ctl[1] : (c->wideRecentParts * 7 + ctl[1]) / 8;
-      c->wideRecentReads = ctl[0] > c->wideRecentReads ? ctl[0] : (c->wideRecentReads * 7 + ctl[0]) / 8;
       if (q.tierHint) {   // remembered by the caller: these reads start on the second stream the next time they are queried
         const T4WidePlan *plans[2] = {(const T4WidePlan *)(o + q.pWplan), (const T4WidePlan *)(o + q.pWplanA)};
         const int cnt[2] = {ctl[0] < n ? ctl[0] : n, ctlA[0] < n ? ctlA[0] : n};
@@ -2308,21 +2302,13 @@ int t4_add_query_pool(t4_index *ix, int n, const char *bases, const int64_t *off
 
 // The two halves of t4_add_query_pool: begin enqueues the call on ix's ctx and returns; the host goes on; end waits and hands the
 // result out (same lifetime rules). tier_hint must stay alive until end. One call in flight per ctx.
-int t4_add_query_pool_begin(t4_index *ix, int n, const char *bases, const int64_t *offsets, const int32_t *barcodes, const int32_t *strands,
-                            int skip_repeats, const double *factors, unsigned char *tier_hint, const int32_t *only_seq) {
-  if (!ix || n <= 0 || !bases || !offsets || !strands || !factors) return T4_ERR_ARG;
-  t4_ctx *c = ix->ctx;
-  if (!ix->committed) return fail(c, T4_ERR_STATE, "index not committed");
-  if (ix->view.firstIsRef) return fail(c, T4_ERR_UNSUPPORTED, "t4_add_query needs a contig set");
-  return aqBegin(c, ix->view, nullptr, nullptr, false, n, bases, offsets, barcodes, strands, skip_repeats, factors, tier_hint, true, only_seq);   // for t4_assembler: lean records (extendOverlaps)
-}
 int t4_add_query_pool_begin2(t4_index *ix, int n, const char *bases, const int64_t *offsets, const int32_t *barcodes, const int32_t *strands,
                              int skip_repeats, const double *factors, unsigned char *tier_hint, const int32_t *only_seq, const int32_t *force_min, int want_cands) {
   if (!ix || n <= 0 || !bases || !offsets || !strands || !factors) return T4_ERR_ARG;
   t4_ctx *c = ix->ctx;
   if (!ix->committed) return fail(c, T4_ERR_STATE, "index not committed");
   if (ix->view.firstIsRef) return fail(c, T4_ERR_UNSUPPORTED, "t4_add_query needs a contig set");
-  return aqBegin(c, ix->view, nullptr, nullptr, false, n, bases, offsets, barcodes, strands, skip_repeats, factors, tier_hint, true, only_seq, force_min, want_cands);
+  return aqBegin(c, ix->view, nullptr, nullptr, false, n, bases, offsets, barcodes, strands, skip_repeats, factors, tier_hint, true, only_seq, force_min, want_cands);   // for t4_assembler: lean records (extendOverlaps)
 }
 // per read of the last finished call begun with want_cands: its candidate records (cnt[i] of them from base[i] of pool, pinned
 // memory valid until the next call) and its eight statistics words (T4QueryArgs::stats8)

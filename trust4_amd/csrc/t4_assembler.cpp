@@ -209,13 +209,6 @@ struct HostIndex {
     v[(size_t)off] = Hint{pos, (uint32_t)code, (uint32_t)(code >> 32)};
   }
   void hintMoved(const Post &p, uint32_t from, uint32_t to) { if (hintGet(p.idx, p.offset) == from) hint[(size_t)p.idx][(size_t)p.offset].pos = to; }
-  // the hint of (idx, off) when it names a posting (idx, off) of the list of `code`: no look at the key map at all
-  uint32_t hintOf(int idx, int off, uint64_t code) const {
-    if (idx < 0 || off < 0 || (size_t)idx >= hint.size() || (size_t)off >= hint[(size_t)idx].size()) return NOPOS;
-    const Hint &hp = hint[(size_t)idx][(size_t)off];
-    if (hp.pos == NOPOS || hp.codeLo != (uint32_t)code || hp.codeHi != (uint32_t)(code >> 32)) return NOPOS;
-    return arena[hp.pos].idx == idx && arena[hp.pos].offset == off ? hp.pos : NOPOS;
-  }
   // position in list l of a posting (idx, off), NOPOS when the list holds none
   uint32_t findPost(const ListRef &l, int idx, int off) {
     const uint32_t h = hintGet(idx, off);
@@ -637,7 +630,7 @@ struct t4_assembler : IndexListener {
     // at most 50 on the best one's (the order-dependent pre-filters of SeqSet.hpp:1705-1794 stay off) and at most 100 groups of four
     // hits (novelMinHitRequired stays 3, SeqSet.hpp:813-823), what the read's result takes from one contig is independent of every
     // other contig: a commit that touches contig c of such an entry leaves the entry PARTIAL -- it keeps its records of the other
-    // contigs -- and only the overlaps with c are asked for again (t4_add_query_pool_begin, only_seq).
+    // contigs -- and only the overlaps with c are asked for again (t4_add_query_pool_begin2, only_seq).
     int nAll = 0, nOther = 0, n4 = 0, nAllBound = 0, restrictedCount = 0;
     // ---- the candidate store: what lets an entry with MORE than 50 candidate overlaps, or with more than 100 groups of
     // four hits, keep its other contigs when one contig changes. cands: every overlap of the read on the strand of the best one as it
@@ -690,7 +683,7 @@ struct t4_assembler : IndexListener {
   int threads = 1;
   std::unique_ptr<HelperPool> helpers;
   int64_t nextUid = 1;
-  struct KOcc { int64_t uid; int slot; unsigned char f, r; short pos; int next; };   // an occurrence of a key in a window read: the k-mer of the read as given that starts at pos (its reverse complement is the k-mer of the reverse strand at len - k - pos)
+  struct KOcc { int64_t uid; int slot; short pos; int next; };   // an occurrence of a key in a window read: the k-mer of the read as given that starts at pos (its reverse complement is the k-mer of the reverse strand at len - k - pos)
   // inverted map key -> window reads that hold it: open addressing on (code, bucket), chains of KOcc nodes; references of
   // retired reads stay (their uid no longer matches) until the map is rebuilt
   struct WinKmers {
@@ -752,7 +745,7 @@ struct t4_assembler : IndexListener {
   int64_t toleratedStable = 0, invLongLists = 0;
   int64_t wideServed = 0, wideGroupRecords = 0, wideMispredicted = 0;
   int64_t restrictedMarks = 0, restrictedMerged = 0, restrictedFallbacks = 0, restrictedStale = 0, restrictedMulti = 0;
-  bool restrictOn = true, candStore = true;
+  bool candStore = true;
   int64_t candRecords = 0, candMerges = 0, candFallbackUncut = 0, candFallbackStats = 0, candFallbackStrand = 0, candFallbackOther = 0, candRecut = 0, candSelfChecks = 0, candMergesBig = 0, candMergesStats = 0, candExactStats = 0, candRaised = 0;
   bool mergeRestricted(Cached &c, int pc, int k2, const t4_overlap *ov, const t4_overlap *ex, const int32_t *rets, const t4_cand *nc, int ncnt, const int32_t *s8);
   static void replayScan(const std::vector<t4_cand> &cands, const std::vector<Seq> &seqs, int len, int radius, double repeatSim, std::vector<unsigned char> &cut);
@@ -762,7 +755,7 @@ struct t4_assembler : IndexListener {
   // reference genes only and a contig set holds none; the query reports a result that came from it as nOther = 32767, which keeps
   // the entry out of here.)
   bool eligibleForRestricted(const Cached &e) {
-    if (!restrictOn || !e.valid || e.skip || e.barcode != -1) { ++whyNot[5]; return false; }
+    if (!e.valid || e.skip || e.barcode != -1) { ++whyNot[5]; return false; }
     if (!e.auxOk) { ++whyNot[4]; return false; }
     if (e.fragile) { ++whyNot[0]; return false; }
     if (e.nOther != 0) { ++whyNot[1]; return false; }
@@ -772,7 +765,7 @@ struct t4_assembler : IndexListener {
     return true;
   }
   void rebuildGroup(Cached &e, int c);
-  bool wideQueries = true; int wideHitLimit = 3072;   // what t4_add_query_pool_begin will do with a read of that many emitted hits (set in ensureLanes)
+  bool wideQueries = true; int wideHitLimit = 3072;   // what t4_add_query_pool_begin2 will do with a read of that many emitted hits (set in ensureLanes)
   int emittedHits(Cached &e);
   int64_t headWholeWhy[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int64_t toleranceChecks = 0, toleranceCheckKills = 0, groupSelfChecks = 0, fragileChecks = 0;
@@ -782,9 +775,9 @@ struct t4_assembler : IndexListener {
 
   // testing / development aids, read from the environment ONCE per builder (none changes a result; DESIGN 7b lists them)
   struct Knobs {
-    bool verifyWindow = false, noStableStats = false, wideQueries = true, candStore = true, restrictOn = true, predictHints = true, useMarks = true, contigKills = false, exactTolerance = true, fragileChecks = false;
+    bool verifyWindow = false, noStableStats = false, wideQueries = true, candStore = true, exactTolerance = true, fragileChecks = false;
     int wideHitLimit = 3072;
-    int lanes = 1, queryAhead = 0, minBatch = 4, harvestDelay = 0, lightAhead = 0, maxPending = 8, restrictAhead = 0;
+    int lanes = 1, queryAhead = 0, minBatch = 4, harvestDelay = 0, maxPending = 8;
     FILE *roundLog = nullptr;
     Knobs() {
       auto num = [](const char *n, int d) { const char *e = getenv(n); return e ? atoi(e) : d; };
@@ -795,14 +788,8 @@ struct t4_assembler : IndexListener {
       { const int lim = num("T4_AQ_CAP_LIMIT", 0); wideHitLimit = lim > 0 ? lim : num("T4_WIDE_MIN_HITS", 3072); }
       fragileChecks = getenv("T4_FRAGILE_CHECKS") != nullptr;   // entries of reads with lists beyond 10000 postings take booked edits and are checked (threshold, removeOnlyRepeats, head of the hit array) instead of falling to every edit
       exactTolerance = !getenv("T4_NO_EXACT_TOLERANCE");   // A-B aid: the budget rule for every entry whose query did not certify its threshold (until round 6)
-      contigKills = getenv("T4_CONTIG_KILLS") != nullptr;   // A-B aid: a merge ends every window entry with a hit on the merged contigs (until round 6)
-      useMarks = !getenv("T4_NO_MARKS");        // A-B aid: restricted re-queries walk the read's posting lists as in round 4
-      predictHints = !getenv("T4_NO_PREDICT");   // A-B aid: no look at the reads of the next whole-query round
       candStore = !getenv("T4_CANDS_OFF");      // testing / A-B aid: the restricted path as round 4 had it (at most 44 candidates, ~100 groups of four hits)
-      restrictOn = !getenv("T4_RESTRICT_OFF");  // testing / A-B aid: every invalidated entry is queried again in full
-      restrictAhead = num("T4_RESTRICT_AHEAD", 0);   // restricted re-queries only for entries within this many places of the head (0: as far as whole queries reach; -n: n/2 x the reads a round has recently served + 4)
       maxPending = num("T4_MAX_PENDING", 8);   // contigs a window entry may wait for at a time (1: round 4's rule, a second contig ends the entry)
-      lightAhead = num("T4_LIGHT_AHEAD", 0);    // whole queries ride with a head that waits for a restricted re-query only when they are this near the head (0: the head's own); -1: every round carries every entry without a result (round 4)
       if (getenv("T4_ROUND_LOG")) roundLog = fopen(getenv("T4_ROUND_LOG"), "w");   // one line per launch: reads, kernel ms, per read us / overlaps / tier / killed in flight
     }
     ~Knobs() { if (roundLog) fclose(roundLog); }
@@ -1729,7 +1716,7 @@ void t4_assembler::registerKmers(Cached &e, int slotId, int shard) {
       const int h = index.bucket(kc.code, e.barcode);
       const int sh = shardOf(kc.code, h);
       if (shard >= 0 && sh != shard) continue;
-      winShard[sh].add(kc.code, h, KOcc{e.uid, slotId, 1, 0, (short)(i - k + 1), -1});
+      winShard[sh].add(kc.code, h, KOcc{e.uid, slotId, (short)(i - k + 1), -1});
       if (shard < 0) winKmerRefs += 1;
     }
     if (shard <= 0) e.repeatNear = near;
@@ -1953,7 +1940,7 @@ void t4_assembler::processEvents() {
       if (!e.standing()) continue;
       if (e.inflight && e.expectWide && !e.hasDev) { kill(e, invContig); continue; }   // its dependency records are still on their way: nothing to examine the change against
       if (e.isPending(ev.c)) {   // (its records and its group of this contig are stale already: any change of it counts)
-        if (ev.kind == 2 && knobs.contigKills) kill(e, invContig); else touch(e, ev.c, ev.kind == 0 ? invRegion : ev.kind == 1 ? invShift : invContig);
+        touch(e, ev.c, ev.kind == 0 ? invRegion : ev.kind == 1 ? invShift : invContig);
         continue;
       }
       const int margin = radius + 2;
@@ -1967,7 +1954,6 @@ void t4_assembler::processEvents() {
           // of a released contig (it has no posting left), the overlaps with the new consensus of the survivor -- and the removals and
           // insertions of the merge reach the entry's small groups as index events like any other edit. A group below three hits holds
           // no candidate (SeqSet.hpp:923-925) and is left to those events.
-          if (knobs.contigKills) { kill(e, invContig); break; }
           if (g->cnt >= 3 || g->lo <= g->hi) { touch(e, ev.c, invContig); break; }
           continue;
         }
@@ -2170,7 +2156,7 @@ int t4_assembler::launchOn(Lane &L, const std::vector<int> &todo, int repetitive
   { auto t0 = std::chrono::steady_clock::now(); rc = bringUpToDate(L); secDelta += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); if (rc) return rc; }
   const int m = (int)todo.size();
   ts.lap(TS_DELTA);
-  wideQueries = knobs.wideQueries; wideHitLimit = knobs.wideHitLimit;   // what t4_add_query_pool_begin does with a heavy read under the testing aids of csrc/t4_api.hip
+  wideQueries = knobs.wideQueries; wideHitLimit = knobs.wideHitLimit;   // what t4_add_query_pool_begin2 does with a heavy read under the testing aids of csrc/t4_api.hip
   // one item per whole query, one per contig a partial entry waits for (the items of an entry are adjacent)
   L.slots.clear(); L.uids.clear(); L.hint.clear(); L.bcs.clear(); L.sts.clear(); L.fac.clear(); L.only.clear(); L.force.clear();
   L.bases.clear(); L.offs.assign(1, 0); L.repetitive = repetitive;
@@ -2203,7 +2189,7 @@ int t4_assembler::launchOn(Lane &L, const std::vector<int> &todo, int repetitive
     auto tq0 = std::chrono::steady_clock::now();
     candStore = knobs.candStore;
     rc = t4_add_query_pool_begin2(L.dev, mi, L.bases.data(), L.offs.data(), L.bcs.data(), L.sts.data(), repetitive, L.fac.data(), L.hint.data(), anyOnly ? L.only.data() : nullptr,
-                                  anyOnly ? L.force.data() : nullptr, (candStore ? 1 : 0) | (knobs.useMarks ? 2 : 0));
+                                  anyOnly ? L.force.data() : nullptr, candStore ? 1 : 0);
     secQuery += std::chrono::duration<double>(std::chrono::steady_clock::now() - tq0).count();
   }
   ts.lap(TS_LAUNCH_CALL);
@@ -2216,7 +2202,6 @@ int t4_assembler::launchOn(Lane &L, const std::vector<int> &todo, int repetitive
   auto tg1 = std::chrono::steady_clock::now();
   std::atomic<int> nextG(0);
   std::atomic<int> regShard(0);
-  restrictOn = knobs.restrictOn;
   std::vector<int> regList;
   for (int sl : todo) if (!pool[sl]->registered) regList.push_back(sl);
   const auto registerNew = [&]() {   // a shard of the map per taker (the first WK_SHARDS threads that come by)
@@ -2250,7 +2235,7 @@ int t4_assembler::launchOn(Lane &L, const std::vector<int> &todo, int repetitive
   // it is now; it is a hint: either path serves any read.
   std::vector<int> predict;
   std::atomic<int> nextP(0);
-  if (wideQueries && !repetitive && mi > 0 && !anyOnlyAll && knobs.predictHints) {
+  if (wideQueries && !repetitive && mi > 0 && !anyOnlyAll) {
     size_t seen = 0;
     for (size_t i = 0; i < order.size() && seen < 48; ++i) {
       Cached &e = *pool[order[i]];
@@ -2789,7 +2774,6 @@ int t4_assembler::pumpLive(bool needHead, int repetitive) {
   // Entries far behind the head rarely survive until they are consumed: (re-)query only as far ahead as a few times what a launch
   // for the head has recently served (every read queried adds to the latency of the launch: it ends with its slowest read)
   const size_t ahead = fixedAhead > 0 ? (size_t)fixedAhead : (lanes.size() > 1 ? 24 : (size_t)(3.0 * runEma) + 12);   // (factors 2 and 4 measured in round 5 with light rounds: 66.4 / 64.1 s against 61.3 s on C2, profiles/r05f)
-  const size_t restrictAhead = knobs.restrictAhead > 0 ? (size_t)knobs.restrictAhead : knobs.restrictAhead < 0 ? (size_t)(-knobs.restrictAhead * 0.5 * runEma) + 4 : 0;
   for (;;) {
     // T4_LIVE_HARVEST_DELAY=n (testing aid): a finished launch is only noticed n calls later, so that commits pile up against queries in flight
     const int harvestDelay = knobs.harvestDelay;
@@ -2813,9 +2797,6 @@ int t4_assembler::pumpLive(bool needHead, int repetitive) {
       // two classes of work: restricted re-queries (one contig of an entry that keeps the rest: tens of microseconds) and whole
       // queries (hundreds; a read the wide query serves, more). With two lanes the head's restricted re-query does not wait for
       // the whole queries of the entries behind it.
-      // (an entry that waits for a contig far behind the head is likely to meet another change of that contig before it is served -- the
-      // reads of a clone extend the same contig end one after the other --: its re-query waits until it comes within restrictAhead places)
-      if (c.partial && restrictAhead > 0 && i >= restrictAhead) continue;
       (c.partial ? light : heavy).push_back(order[i]);
     }
     const bool headWaits_ = !head.valid && !head.inflight;
@@ -2830,16 +2811,11 @@ int t4_assembler::pumpLive(bool needHead, int repetitive) {
       // the head's launch carries the entries of its own weight class; the other class goes beside it when a lane is free
       std::vector<int> &mine = head.partial ? light : heavy, &other = head.partial ? heavy : light;
       if (lanes.size() == 1) {   // one launch: the heavy ones run beside the others on the ctx's second stream
-        // A round lasts as long as its slowest read. When the head only waits for a restricted re-query (tens of microseconds), whole
-        // queries of entries further back than `lightAhead` places stay out of its round: they go with the next round whose head needs
-        // a whole query itself (or when they come within reach of the head).
-        if (head.partial && knobs.lightAhead >= 0) {
-          std::vector<int> near;
-          for (size_t i = 0; i < order.size() && i < ahead && (int)i <= knobs.lightAhead; ++i) { Cached &c = *pool[order[i]]; if (!c.valid && !c.inflight && !c.partial) near.push_back(order[i]); }
-          other.swap(near);
-          ++lightRounds;
-        }
-        mine.insert(mine.end(), other.begin(), other.end()); other.clear();
+        // A round lasts as long as its slowest read. When the head only waits for a restricted re-query (tens of microseconds), the
+        // whole queries stay out of its round: they go with the next round whose head needs a whole query itself.
+        if (head.partial) ++lightRounds;
+        else mine.insert(mine.end(), other.begin(), other.end());
+        other.clear();
       }
       {
         const double served = (double)(cacheHits - hitsAtLastRound);

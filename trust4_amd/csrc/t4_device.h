@@ -99,7 +99,6 @@ struct T4WidePlan { int pBase, P, Wd /* unused since the partitions follow the h
 struct T4Wide {
   int enabled;
   int maxReads, maxPart, pcap, maxOvPart, safetyNum /* partitions are planned for pcap * 16 / safetyNum hits */, maxPartPerRead;
-  int samplePerPart;         // hits sampled per planned partition for the partition boundaries (0: 4096 per read whatever it plans)
   int minHits;               // a read goes wide when its seed stage emits more hits than this (or meets a list beyond 10000 postings, or outgrows the global-scratch tier)
   int *ctl;                  // [0] reads, [1] partitions, [2] overflow flags (1 reads, 2 partitions, 4 keys of a partition, 8 overlaps of a partition, 16 group pool), [3] group pool cursor
   T4WidePlan *plan;          // [maxReads]
@@ -182,7 +181,6 @@ struct T4CandArgs {
   int *candBase, *candCnt;   // null with candOut
   int *stats8;
   const int *forceMin;       // nullable
-  int useMarks;              // the image's predicate bytes carry posting marks (T4_PW_MARK_*): restricted re-queries read a contig's postings off the contig
 };
 // Bits 5-6 of a contig's predicate byte at offset o: the number of postings (contig, o) the index holds (0-3); bit 7 of the byte at
 // offset 0: the marks of this contig are not to be trusted (an offset with more than three postings). Written by the ordered

@@ -49,19 +49,16 @@ int t4_add_query_pool(t4_index *ix, int n, const char *bases, const int64_t *off
 // the same in two halves, so that the caller's host work overlaps the kernels: begin enqueues, done polls (1 = finished or idle),
 // end waits and returns the result. tier_hint must stay alive until end; one call in flight per ctx.
 // only_seq (nullable): only_seq[i] >= 0 asks for the overlaps of read i with that one contig alone -- all of them, both strands,
-// scored and extended, none of the steps that look across contigs applied (the restricted re-query of a window entry)
-int t4_add_query_pool_begin(t4_index *ix, int n, const char *bases, const int64_t *offsets, const int32_t *barcodes, const int32_t *strands,
-                            int skip_repeats, const double *factors, unsigned char *tier_hint, const int32_t *only_seq);
+// scored and extended, none of the steps that look across contigs applied (the restricted re-query of a window entry). It reads the
+// contig's postings off the posting marks of the image's predicate bytes (t4_device.h T4_PW_MARK_*, written by t4_assembler::makeDelta).
 // The candidate store: with want_cands the call also returns, per read, EVERY scored overlap of the pass on the strand of
 // the best one as it stands before the similarity cut (a restricted re-query: every overlap with its one contig) in the order of the
 // scan of SeqSet.hpp:1673-2094 -- pre-score key, scored fields, whether the pre-filters of 1705-1794 cut it -- and eight statistics
 // words per read: per strand (minus, plus) the groups of >= 4 hits, of >= 5 hits, the largest group (true sizes; a restricted
 // re-query: of its one contig) and the novelMinHitRequired the pass used (SeqSet.hpp:784-823); a restricted re-query adds the hull of
 // the read's projections along the contig's diagonals with three or more hits (lo minus / plus, hi minus / plus; lo > hi: none):
-// T4_QUERY_STATS words per read. want_cands: 1 = return the candidate records; | 2 = the image's predicate bytes carry posting marks
-// (bits 5-6 of the byte at offset o: postings (contig, o) in the index, bit 7 of a contig's first byte: marks not to be trusted --
-// t4_assembler::makeDelta writes them), so a restricted re-query reads the contig's postings off the contig. force_min (nullable, restricted
-// re-queries): that threshold for the one contig's groups, minus | plus << 16 (0: three hits).
+// T4_QUERY_STATS words per read. want_cands: 1 = return the candidate records. force_min (nullable, restricted re-queries): that
+// threshold for the one contig's groups, minus | plus << 16 (0: three hits).
 #define T4_QUERY_STATS 12
 typedef struct { int32_t seqIdx, ss, se; int16_t rs, re, m0, matchCnt, indelCnt; uint16_t flags; } t4_cand;   // flags: 1 plus strand, 2 scoring left similarity 0, 4 cut by the pre-filters
 int t4_add_query_pool_begin2(t4_index *ix, int n, const char *bases, const int64_t *offsets, const int32_t *barcodes, const int32_t *strands,

@@ -757,7 +757,7 @@ struct WaveState { // wave-uniform scalars kept in LDS
   int nvN4[2], nvN5[2], nvSmax[2];   // groups of at least 4 / 5 hits and the largest group, TRUE sizes (the statistics measure a group one short or in full)
   int statsStable;                   // no pass of this read so far whose novelMinHitRequired could move (see overlapsFromKeys)
   int hullLo[2], hullHi[2];          // restricted re-query: per strand, hull of the read's projections along the diagonals that hold three or more hits with the contig (lo > hi: none)
-  int useMarks;                      // restricted re-query: read the contig's postings off its posting marks (T4CandArgs::useMarks)
+  int spare;                         // unused: keeps the struct at 480 bytes, and with it where the kernels' other LDS arrays land (one int less cost the annotation kernel 3 %)
   int forceMin[2];                   // restricted re-query: novelMinHitRequired per strand as the entry's whole query had it (0: three hits), T4QueryArgs::forceMin
   int vjRescue;                      // the pass ended in the VJ-junction rescue (GetVJOverlapsFromHits looks ACROSS sequences: such a result is not the sum of per-contig parts)
   int nAll, nOther, strand0;          // GetOverlapsFromRead: overlaps on the strand of the best one (before the similarity cut), on the other strand, that strand
@@ -1122,7 +1122,7 @@ __device__ int expandHitsOnly(const T4IndexView &ix, WaveMem &wm, WaveState *ws,
   return n <= wm.hitLimit ? n : -1;
 }
 
-// The same hits read off the CONTIG instead of the read's posting lists (restricted re-query with posting marks, T4CandArgs::useMarks):
+// The same hits read off the CONTIG instead of the read's posting lists (restricted re-query, by the posting marks of t4_device.h T4_PW_MARK_*):
 // a posting (seq, o) exists for every offset o whose predicate byte carries a mark, its code is the contig's k-mer at o (the index
 // is kept in step with the consensus: KmerIndex entries are removed and rebuilt whenever a consensus base changes, SeqSet.hpp:4537-
 // 4588, 11058-11080), and it is a hit of read position q exactly when q was emitted by the seed stage and holds that code. A heavy
@@ -2400,8 +2400,8 @@ __device__ int seedChainPass(const T4IndexView &ix, WaveMem &wm, WaveState *ws, 
   int H = NOVEL ? seedPositionsNovel(ix, wm, segLen, strandArg, barcode, allowTotalSkip, posStart, posPref, ws->red, wm.keys, ws)
                 : seedPositions(ix, wm, segLen, strandArg, barcode, allowTotalSkip, posStart, posPref, ws->red);   // the key array is free until the hits are expanded
   if (NOVEL && onlySeq >= 0) {   // restricted re-query: the hits with one contig (a few hundred at most), whatever the read's total
-    int Hv = -2;
-    if (ws->useMarks) { __syncthreads(); Hv = expandHitsContig(ix, wm, ws, nk, onlySeq, posPref); }
+    __syncthreads();
+    int Hv = expandHitsContig(ix, wm, ws, nk, onlySeq, posPref);
     const bool offContig = Hv != -2;
     if (!offContig) Hv = expandHitsOnly(ix, wm, ws, nk, H, onlySeq, posStart, posPref);
     if (Hv < 0) return -1;
@@ -3588,7 +3588,7 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
   const int lane = tid(), NT = nthr();
   const int len = bv.len[r];
   unsigned long long hitTotal = 0;
-  if (lane == 0) { ws->overflow = 0; ws->unsupported = 0; ws->finCount = 0; ws->nContig = 0; ws->ovCount = 0; ws->statsStable = 1; ws->wideWant = 0; ws->nvN4[0] = ws->nvN4[1] = 0; ws->forceMin[0] = ws->forceMin[1] = 0; ws->useMarks = 0; }
+  if (lane == 0) { ws->overflow = 0; ws->unsupported = 0; ws->finCount = 0; ws->nContig = 0; ws->ovCount = 0; ws->statsStable = 1; ws->wideWant = 0; ws->nvN4[0] = ws->nvN4[1] = 0; ws->forceMin[0] = ws->forceMin[1] = 0; }
 #ifdef T4_PHASE_TIMING
   if (lane == 0) { ws->phaseT0 = clock64(); ws->phaseBase = wm.ldsArrays ? 0 : 32; ws->curPhase = ws->phaseBase; }
 #endif
@@ -3607,7 +3607,6 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
     if (lane == 0 && qa.cs) {
       const T4CandArgs *cs = qa.cs;
       if (onlySeq >= 0 && cs->forceMin) { const int f = cs->forceMin[r]; ws->forceMin[0] = f & 0xFFFF; ws->forceMin[1] = (f >> 16) & 0xFFFF; }
-      if (onlySeq >= 0) ws->useMarks = cs->useMarks;
       if (cs->candCnt) cs->candCnt[r] = 0;
     }
     loadSegment(bv, r, 0, len, wm);

@@ -25,6 +25,7 @@
 
 #define T4_WIDE_SEEDS (2 * T4_MAXL + 2)
 #define T4_WIDE_OVBITS 9           // overlap records of one partition: 512
+#define T4_WIDE_PART_SAMPLES 256   // hits sampled per planned partition for its boundaries (at least 512, at most 4 096 per read: profiles/r06g)
 
 // ws->red[13..15] are free for this (the scans use the first eight words)
 __device__ T4_NI void wideDeferRead(const T4IndexView &ix, WaveMem &wm, WaveState *ws, const T4Wide &wd, int len, int strandArg, long long r,
@@ -69,8 +70,8 @@ __device__ T4_NI void wideDeferRead(const T4IndexView &ix, WaveMem &wm, WaveStat
     int *bd = wd.bounds + (size_t)slot * (T4_WIDE_MAXP + 1);
     unsigned *smp = (unsigned *)wm.keys;   // (the key array is free: the seed stage's code buffer died with it)
     int nS = 2 * wm.cap < 4096 ? 2 * wm.cap : 4096;
-    if (wd.samplePerPart > 0) {   // (a read that plans four partitions does not need 4 096 samples to cut them: gathers and sort of the sample are on the round's critical path)
-      int want = wd.samplePerPart * P;
+    {   // (a read that plans four partitions does not need 4 096 samples to cut them: gathers and sort of the sample are on the round's critical path)
+      int want = T4_WIDE_PART_SAMPLES * P;
       if (want < 512) want = 512;
       if (want < nS) nS = want;
     }
