@@ -150,6 +150,7 @@ struct t4_ctx {
   bool wideInit = false;
   unsigned char *grpPoolHost = nullptr;   // pinned; T4Wide::grpPool is its device address
   int64_t wideReads = 0, wideParts = 0, wideRetries = 0, wideGroups = 0;
+  int64_t aqDeferredReads = 0;   // reads whose ExtendOverlap calls the query kernel left to extendKernel (T4QueryArgs::extendLater)
   int64_t wideCalls = 0, wideCallsDeferred = 0, wideCallsDirect = 0;   // calls with the wide query on; those whose query kernel deferred a read; those with reads on the second stream
   int wideSafetyKeep = 32, wideCallsSinceRepeat = 0;   // partition load factor that recent calls needed (of sixteenths: 32 = partitions planned half full); decays back when nothing overflows
   int64_t wideFlagCounts[6] = {0, 0, 0, 0, 0, 0};     // calls repeated because: reads, partitions, keys of a partition, overlaps of a partition, dependency records, other
@@ -1035,7 +1036,7 @@ int runQuery(t4_index *ix, t4_batch *b, T4QueryArgs qa, bool useBarcode, bool no
   for (long long i = 0; i < n; ++i)
     if (status[i] != 0)
       return fail(c, T4_ERR_UNSUPPORTED, "read %lld exceeds the engine limits (status %d: %s)", i, status[i],
-                  status[i] == 2 ? "more than 262144 k-mer hits or 16384 overlaps" : "gap DP or contig count beyond scratch");
+                  status[i] == 2 ? "more than 262144 k-mer hits or 16384 overlaps" : "a posting list beyond 10000 entries, or gap DP or contig count beyond scratch");
   return T4_OK;
 }
 
@@ -1704,7 +1705,7 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   q.pNext2 = al8(q.pNext + sizeof(int) * (size_t)n); q.pBase = al8(q.pNext2 + sizeof(int) * (size_t)n);
   q.pTick = al8(q.pBase + sizeof(int) * (size_t)n); q.pStab = al8(q.pTick + sizeof(int) * (size_t)n); q.pAux = al8(q.pStab + sizeof(int) * (size_t)n);
   q.pN4 = al8(q.pAux + sizeof(int) * (size_t)n); q.pCb = al8(q.pN4 + sizeof(int) * (size_t)n); q.pCc = al8(q.pCb + sizeof(int) * (size_t)n);
-  q.pS8 = al8(q.pCc + sizeof(int) * (size_t)n); q.pTail = al8(q.pS8 + sizeof(int) * T4_QSTATS * (size_t)n);   // tail: overflow1 | overflow2 | hits (8 B) | pool cursor | dir overflow | cand cursor | cand overflow
+  q.pS8 = al8(q.pCc + sizeof(int) * (size_t)n); q.pTail = al8(q.pS8 + sizeof(int) * T4_QSTATS * (size_t)n);   // tail: overflow1 | overflow2 | hits (8 B) | pool cursor | dir overflow | cand cursor | cand overflow | reads deferred to extendKernel
   q.pWctl = q.pTail + 48; q.pWplan = q.pWctl + 32; q.pWstat = al8(q.pWplan + sizeof(T4WidePlan) * (size_t)n);
   q.pWctlA = al8(q.pWstat + sizeof(int) * T4_WIDE_STAT * (size_t)n); q.pWplanA = q.pWctlA + 32; q.pWstatA = al8(q.pWplanA + sizeof(T4WidePlan) * (size_t)n);
   q.outBytes = al8(q.pWstatA + sizeof(int) * T4_WIDE_STAT * (size_t)n);
@@ -2145,7 +2146,7 @@ int aqEnd(t4_ctx *c, AqResult *res) {
       if (status[i] == 3) poolFull = true;
       else if (status[i] == 5) continue;   // a restricted re-query that one workgroup's arrays could not hold: reported to the caller (t4_add_query_last_aux)
       else if (status[i]) return fail(c, T4_ERR_UNSUPPORTED, "read %d exceeds the engine limits (status %d: %s)", i, status[i],
-                                      status[i] == 2 ? "more k-mer hits or overlaps than the global tier holds" : "gap DP or contig count beyond scratch");
+                                      status[i] == 2 ? "more k-mer hits or overlaps than the global tier holds" : "a posting list beyond 10000 entries, or gap DP or contig count beyond scratch");
     }
     if (*(const unsigned *)(o + pTail + 28)) return fail(c, T4_ERR_UNSUPPORTED, "an overhang alignment of this batch exceeds the extension kernel's direction buffer");
     if (q.wantCands && *(const int *)(o + pTail + 36)) {   // more candidate records than their pool holds: a larger pool, and the whole call again
@@ -2169,6 +2170,7 @@ int aqEnd(t4_ctx *c, AqResult *res) {
     }
     const size_t rec = (size_t)c->aqPoolCap;
     c->aqRecords += *(const unsigned *)(o + pTail + 24);
+    c->aqDeferredReads += *(const unsigned *)(o + pTail + 40);
     if (q.wantCands) c->candRecords += *(const unsigned *)(o + pTail + 32);
     c->aqHits += (int64_t) * (const unsigned long long *)(o + pTail + 16);
     c->aqLastTicks = (const int32_t *)(o + q.pTick); c->aqLastN = n;
@@ -2275,6 +2277,13 @@ int t4_add_query_last_aux(t4_ctx *c, const int32_t **aux, const int32_t **n4, co
 int t4_add_query_wide_stats(t4_ctx *c, int64_t *out4) {
   if (!c || !out4) return T4_ERR_ARG;
   out4[0] = c->wideReads; out4[1] = c->wideParts; out4[2] = c->wideRetries; out4[3] = c->wideGroups;
+  return T4_OK;
+}
+
+// reads of this ctx's AddRead query calls whose ExtendOverlap calls ran in extendKernel (more than T4_AQ_EXTEND_DEFER overlaps)
+int t4_add_query_defer_stats(t4_ctx *c, int64_t *out1) {
+  if (!c || !out1) return T4_ERR_ARG;
+  out1[0] = c->aqDeferredReads;
   return T4_OK;
 }
 

@@ -79,6 +79,7 @@ typedef struct { uint32_t key, cnt; int32_t lo, hi; } t4_grp;   // key = contig 
 // bits 24-26 its hits of lists of at most 10000 postings, capped at 4; bit 27 whether its hit lowest on the read is one)
 int t4_add_query_groups(t4_ctx *ctx, int i, const t4_grp **groups, int *n, int *huge, int *n4);
 int t4_add_query_wide_stats(t4_ctx *ctx, int64_t *out4);
+int t4_add_query_defer_stats(t4_ctx *ctx, int64_t *out1);
 int t4_add_query_last_call(t4_ctx *ctx, double *kernel_ms, const int32_t **ticks10ns, int *n);   // development aid (T4_ROUND_LOG)
 
 }  // extern "C"

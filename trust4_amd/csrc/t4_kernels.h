@@ -2435,12 +2435,13 @@ __device__ int seedChainPass(const T4IndexView &ix, WaveMem &wm, WaveState *ws, 
     __syncthreads();
     return H;
   }
-  if (NOVEL && !allowTotalSkip && !vjOnly && filter == 1 && H > 10000) {
+  if (!allowTotalSkip && !vjOnly && filter == 1 && H > 10000) {
     // a posting list beyond 10000 entries switches on removeOnlyRepeats and the run-relative repeats test (SeqSet.hpp:802, 876,
-    // 934-940): the wide query replays them, the single-workgroup tiers do not
+    // 934-940): the wide query replays them, the single-workgroup tiers do not -- in every variant (t4_overlaps and the rough
+    // annotation too) such a read is refused, not answered without them
     int huge = 0;
     for (int q = lane; q < 2 * nk; q += NT) if (posPref[q + 1] - posPref[q] > 10000u) huge = 1;
-    if (blockSum(huge, ws->red)) { if (ws->wideWant) return -3; if (lane == 0) ws->unsupported = 1; }
+    if (blockSum(huge, ws->red)) { if (NOVEL && ws->wideWant) return -3; if (lane == 0) ws->unsupported = 1; }
   }
   if (NOVEL && ws->wideWant && H > ws->wideWant && !allowTotalSkip && !vjOnly && filter == 1) return -3;   // heavy enough for the wide query (t4_wide.h)
   if (H > wm.hitLimit) return (NOVEL && ws->wideWant && !wm.ldsArrays && !allowTotalSkip && !vjOnly && filter == 1) ? -3 : -1;
@@ -3659,7 +3660,7 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
       for (int i = lane; i < n; i += NT) qa.recRead[base + i] = defer ? (int)r : -1;
       if (defer) {
         for (int i = lane; i < n; i += NT) storeOverlap(qa.outDev + base + i, wm.fin[i]);
-        if (lane == 0) qa.counts[r] = ret;
+        if (lane == 0) { qa.counts[r] = ret; atomicAdd(qa.poolCursor + 4, 1u); }   // statistics: reads deferred (t4_add_query_defer_stats)
         return true;
       }
     }
