@@ -190,9 +190,16 @@ int t4_consensus_recompute(t4_index *ix, t4_batch *b, const t4_overlap *assign, 
  * for n independent (target, pattern) pairs given as CSR offsets; out4[4*i..] = GetAlignStats of
  * the reference's alignment (matches, mismatches, indels) and a status word (0 ok, 1 beyond the
  * engine's gap limits). impl 0 = the forward-only LDS formulation the overlap scorer uses (falls back
- * to the traceback formulation for wide bands), impl 1 = traceback formulation only, impl 2 = one alignment per
+ * to the traceback formulation for bands wider than 32 columns), impl 1 = traceback formulation only, impl 2 = one alignment per
  * wavefront (status 2 in out4[3] for bands wider than 64 columns), impl 3 = eight alignments per wavefront, two per
- * 16-lane DPP row (status 2 for bands wider than 16 columns): the two formulations overlap scoring runs on the GPU. */
+ * 16-lane DPP row (status 2 for bands wider than 16 columns): the two formulations overlap scoring runs on the GPU.
+ * The status word is a function of the two lengths alone (band = 11 + |lent - lenp| columns; counts are 0 when it is not 0):
+ *   - a pattern of more than 320 bases: 1 (impl 0, 1, 4) or 2 (impl 2, 3), whatever the target -- the kernel stages the pattern first;
+ *   - otherwise an empty side: 0 (no alignment; impl 3 answers 2 when the other side exceeds 320 bases);
+ *   - impl 0, 1, 4: 1 for a target of more than 320 bases, and 1 when the traceback formulation runs (always for impl 1 and 4,
+ *     for bands wider than 32 columns for impl 0) and its direction bytes (lenp + 1) * min(band, lent) exceed 49 152 -- which
+ *     happens INSIDE 320 x 320, for patterns of 318 to 320 bases against targets of about half that (lenp = 320: lent 154 .. 177);
+ *   - impl 2 / 3: 2 for a target of more than 320 bases or a band wider than 64 / 16 columns. */
 int t4_gap_dp(t4_ctx *ctx, int kind, int impl, int n, const int64_t *t_off, const int64_t *p_off,
               const void *t_data, const char *p_chars, int32_t *out4);
 /* impl 4, kind 1: the scratch-row aligner with its traceback; `align` receives the edit string of every alignment (AlignAlgo.hpp:160-205: 0 match, 1 mismatch,

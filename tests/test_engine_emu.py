@@ -266,7 +266,10 @@ def make_dp_cases(seed, n, posweight):
 def check_gap_dp(eng, seed, n):
     """The scoring kernels return what GetOverlapsFromRead reads of an alignment, the GetAlignStats counts (matches, mismatches,
     indels) -- compared here for four formulations of both aligners. The EDIT STRING itself, which only ExtendOverlap reads (of the posWeight aligner, SeqSet.hpp:1203-1235), is
-    compared through impl 4 (the scratch-row aligner with its traceback). The affine aligner's string is never read on this path."""
+    compared through impl 4 (the scratch-row aligner with its traceback). The affine aligner's string is never read on this path.
+    The status word of every case is the one the lengths call for (align_gen.expected_status), and every case of status 0 is
+    compared: none is left out by what the engine answered."""
+    from align_gen import expected_status
     o = Oracle(9)
     for kind in (0, 1):
         T, P = make_dp_cases(seed + kind, n, kind == 1)
@@ -275,19 +278,16 @@ def check_gap_dp(eng, seed, n):
             sc, al = o.global_alignment(t, p) if kind == 0 else o.global_alignment_posweight(t, p)
             exp.append((al.count(0), al.count(1), al.count(2) + al.count(3)))
             exp_al.append(al)
-        if kind == 1:
-            got4, strings = eng.gap_dp(1, T, P, 4)
-            bad = [i for i in range(n) if got4[i, 3] == 0 and (strings[i] != exp_al[i] or tuple(got4[i, :3]) != exp[i])]
-            assert not bad, (bad[:5], [(exp_al[i], strings[i]) for i in bad[:2]])
-            assert (got4[:, 3] == 0).sum() > n * 9 // 10
-        for impl in (0, 1, 2, 3):
-            got = eng.gap_dp(kind, T, P, impl)
-            wide = got[:, 3] == 2     # impl 2 / 3 only: band wider than one wavefront / one 16-lane row (the scorer falls back)
-            assert impl >= 2 or not wide.any()
-            assert ((got[:, 3] == 0) | wide).all() and wide.sum() < (n // 10 if impl == 2 else n // 2)
-            if impl == 3:
-                assert (~wide).sum() > n // 3
-            bad = [i for i in range(n) if not wide[i] and tuple(got[i, :3]) != exp[i]]
+        for impl in (0, 1, 2, 3) + ((4,) if kind == 1 else ()):
+            status = [expected_status(kind, impl, len(t), len(p)) for t, p in zip(T, P)]
+            if impl == 4:
+                got, strings = eng.gap_dp(1, T, P, 4)
+            else:
+                got, strings = eng.gap_dp(kind, T, P, impl), None
+            assert got[:, 3].tolist() == status, (kind, impl, [(i, len(T[i]), len(P[i]), status[i], int(got[i, 3])) for i in range(n) if got[i, 3] != status[i]][:5])
+            ok = [i for i in range(n) if status[i] == 0]
+            assert len(ok) > (n // 2 if impl == 3 else n * 9 // 10)     # (what the random lengths give: most bands fit)
+            bad = [i for i in ok if tuple(got[i, :3]) != exp[i] or (strings is not None and strings[i] != exp_al[i])]
             assert not bad, (kind, impl, bad[:5], [(T[i] if kind == 0 else T[i].tolist(), P[i], exp[i], got[i].tolist()) for i in bad[:2]])
 
 

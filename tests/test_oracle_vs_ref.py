@@ -119,6 +119,43 @@ def test_global_alignment_posweight():
         assert o.global_alignment_posweight(w, p) == r.global_alignment_posweight(w, p), (w.tolist(), p)
 
 
+@pytest.mark.parametrize("kind", [0, 1])
+def test_global_alignment_on_edge_families(kind):
+    """the cases of tests/test_align_edges.py (homopolymers, tandem repeats with indels, leading / trailing gaps, bands of
+    16 / 17, 32 / 33, 64 / 65 columns, sides up to 321 and beyond, the equal-length early returns, the row-0 border quirk, zero-sum
+    and ambiguous columns): scores and edit strings, where almost every cell is a tie"""
+    import align_gen as A
+    o, r = Oracle(9), Ref(9)
+    T, P, tags = A.dp_cases(kind)
+    tied = 0
+    for t, p, tag in zip(T, P, tags):
+        a = o.global_alignment(t, p) if kind == 0 else o.global_alignment_posweight(t, p)
+        b = r.global_alignment(t, p) if kind == 0 else r.global_alignment_posweight(t, p)
+        assert a == b, (tag, t if kind == 0 else t.tolist(), p)
+        tied += any(x >= 2 for x in a[1]) and 0 in a[1]
+    assert tied > len(P) // 4
+
+
+def test_extend_overlap_on_placed_overhangs():
+    """the crafted overlaps of tests/test_align_edges.py: overhangs of 0 .. 383 bases, the 3/4 rule's tie, 2 / 3 mismatches,
+    insertions and deletions, N, zero-sum and ambiguous columns, both mismatch factors"""
+    import align_gen as A
+    es = A.ExtendSet()
+    r = es.ref()
+    cases = A.extend_cases(es)
+    rets = [0, 0]
+    for c in cases:
+        for f in (1.0, 2.0):
+            a, b = es.o.extend_overlap(c["aligned"], f, c["ov"]), r.extend_overlap(c["aligned"], f, c["ov"])
+            assert a == b, (c["planted"], c["ov"], f)
+            rets[a[0]] += 1
+    for i in range(2):
+        rd, ovs = A.sliding_anchor_overlaps(es, i, 128, 40 + i)
+        for ov in ovs:
+            assert es.o.extend_overlap(rd, 1.0, ov) == r.extend_overlap(rd, 1.0, ov), ov
+    assert min(rets) > 200, rets
+
+
 def test_is_mate_overlap():
     o, r = Oracle(9), Ref(9)
     rnd = random.Random(6)

@@ -3521,6 +3521,7 @@ __device__ void extendOverlaps(const T4IndexView &ix, WaveMem &wm, WaveState *ws
             }
           }
         }
+        waveLdsSync();   // lane 0 walks this buffer: the wavefront's next side is staged into it only when the walk is over
       }
       __syncthreads();
     }
