@@ -189,10 +189,11 @@ int t4_consensus_recompute(t4_index *ix, t4_batch *b, const t4_overlap *assign, 
  * AlignAlgo::GlobalAlignment_PosWeight (kind 1; AlignAlgo.hpp:57-216; t_data = 4 int32 weights per base)
  * for n independent (target, pattern) pairs given as CSR offsets; out4[4*i..] = GetAlignStats of
  * the reference's alignment (matches, mismatches, indels) and a status word (0 ok, 1 beyond the
- * engine's gap limits). impl 0 = the forward-only LDS formulation the overlap scorer uses (falls back
+ * engine's gap limits). impl 0 = a forward-only LDS formulation, one alignment per lane, that only this entry point runs (falls back
  * to the traceback formulation for bands wider than 32 columns), impl 1 = traceback formulation only, impl 2 = one alignment per
  * wavefront (status 2 in out4[3] for bands wider than 64 columns), impl 3 = eight alignments per wavefront, two per
- * 16-lane DPP row (status 2 for bands wider than 16 columns): the two formulations overlap scoring runs on the GPU.
+ * 16-lane DPP row (status 2 for bands wider than 16 columns): the two formulations overlap scoring runs on the GPU, with the
+ * scratch-row aligner (impl 4) behind them.
  * The status word is a function of the two lengths alone (band = 11 + |lent - lenp| columns; counts are 0 when it is not 0):
  *   - a pattern of more than 320 bases: 1 (impl 0, 1, 4) or 2 (impl 2, 3), whatever the target -- the kernel stages the pattern first;
  *   - otherwise an empty side: 0 (no alignment; impl 3 answers 2 when the other side exceeds 320 bases);

@@ -142,8 +142,20 @@ static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) {
   memset(p, 0, sizeof(*p)); p->multiProcessorCount = 8; strcpy(p->name, "hipemu"); strcpy(p->gcnArchName, "emu");
   p->totalGlobalMem = 1ull << 34; return hipSuccess;
 }
-template <class T> static inline hipError_t hipMalloc(T **p, size_t n) { *p = (T *)calloc(1, n ? n : 1); return *p ? hipSuccess : hipErrorUnknown; }
-static inline hipError_t hipFree(void *p) { free(p); return hipSuccess; }
+// Bookkeeping of hipMalloc / hipFree for the tests of the error paths (hip_emu.cpp; C symbols, so that ctypes reaches them):
+extern "C" {
+long long hipemu_live_blocks(void);           // hipMalloc blocks not yet given to hipFree
+long long hipemu_malloc_calls(void);          // hipMalloc calls so far
+void hipemu_fail_malloc(long long nth);       // the nth hipMalloc from now fails, once (nth <= 0: none does)
+int hipemu_malloc_enter(void);                // (hipMalloc: counts the call; non-zero when this one is to fail)
+void hipemu_live_add(int d);
+}
+template <class T> static inline hipError_t hipMalloc(T **p, size_t n) {
+  *p = hipemu_malloc_enter() ? nullptr : (T *)calloc(1, n ? n : 1);
+  if (*p) hipemu_live_add(1);
+  return *p ? hipSuccess : hipErrorUnknown;
+}
+static inline hipError_t hipFree(void *p) { if (p) hipemu_live_add(-1); free(p); return hipSuccess; }
 template <class T> static inline hipError_t hipHostMalloc(T **p, size_t n, unsigned = 0) { *p = (T *)calloc(1, n ? n : 1); return hipSuccess; }
 static inline hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
 static inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }

@@ -8,6 +8,19 @@
 #include <condition_variable>
 #include <mutex>
 #include <thread>
+// hipMalloc / hipFree bookkeeping (hip_runtime.h): host threads of the library under test may allocate side by side
+static std::atomic<long long> live_blocks(0), malloc_calls(0), fail_at(0);
+extern "C" {
+long long hipemu_live_blocks(void) { return live_blocks.load(); }
+long long hipemu_malloc_calls(void) { return malloc_calls.load(); }
+void hipemu_fail_malloc(long long nth) { fail_at = nth > 0 ? malloc_calls.load() + nth : 0; }
+int hipemu_malloc_enter(void) {
+  long long want = malloc_calls.fetch_add(1) + 1;
+  return fail_at.compare_exchange_strong(want, 0) ? 1 : 0;
+}
+void hipemu_live_add(int d) { live_blocks += d; }
+}
+
 namespace hipemu {
 // Every host worker thread emulates whole workgroups on its own: all scheduler state is thread-local, workgroups of one
 // launch are handed out through an atomic counter (global-memory atomics of the kernels are real atomics, see hip_runtime.h).

@@ -15,6 +15,7 @@
 #include <atomic>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -220,6 +221,20 @@ template <class T> int devAlloc(t4_ctx *c, T **p, size_t count) {
   HIPCHK(c, hipMalloc(p, sizeof(T) * (count ? count : 1)));
   return T4_OK;
 }
+// Device memory of one call: freed on every way out of the scope (hipFree waits for the work that still uses it).
+template <class T> struct DevBuf {
+  T *p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) : p(o.p) { o.p = nullptr; }   // (move only)
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  int alloc(t4_ctx *c, size_t count) { return devAlloc(c, &p, count); }
+  operator T *() const { return p; }
+};
+// A launch whose arguments are turned into the kernel's parameter types first (a DevBuf into its pointer: the buffer itself is not copied).
+template <class T> struct AsIs { typedef T type; };
+template <class... P> void launch(void (*kernel)(P...), int grid, int block, hipStream_t stream, typename AsIs<P>::type... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, args...);
+}
 
 // SeqSet::GetChainType / GetGeneType (SeqSet.hpp:5132-5155, 5076-5100)
 int chainType(const char *n) {
@@ -242,6 +257,7 @@ inline int nucNum(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 
 // gap-DP scratch for `threads` resident threads (fallback path of bands wider than a wavefront)
 int ensureScratch(t4_ctx *c, int threads) {
   if (threads <= c->maxGrid) return T4_OK;
+  c->maxGrid = 0;   // devAlloc frees first: a growth that fails leaves no capacity behind, and the next call starts over
   int r;
   if ((r = devAlloc(c, &c->dpRows, (size_t)(threads / 64 + 1) * 6 * T4_ROWW * 64))) return r;
   if ((r = devAlloc(c, &c->dpDir, (size_t)threads * T4_DIR_BYTES))) return r;
@@ -251,6 +267,7 @@ int ensureScratch(t4_ctx *c, int threads) {
 int ensureGlobalTier(t4_ctx *c, int grid) {
   if (grid <= c->gGrid) return T4_OK;
   { int g = c->gGrid > 0 ? c->gGrid : 32; while (g < grid) g *= 2; grid = g; }   // 5.4 MB per block: grow rarely
+  c->gGrid = 0;
   int r;
   if ((r = devAlloc(c, &c->gKeys, (size_t)grid * G_CAP))) return r;
   if ((r = devAlloc(c, &c->gPairs, (size_t)grid * G_CAP * 2))) return r;   // pairs + cand, contiguous per block
@@ -262,6 +279,7 @@ int ensureGlobalTier(t4_ctx *c, int grid) {
 }
 int ensurePerCall(t4_ctx *c, long long n) {
   if (n <= c->listCap) return T4_OK;
+  c->listCap = 0;
   int r;
   if ((r = devAlloc(c, &c->lists, (size_t)n * T4_NTIER))) return r;
   if ((r = devAlloc(c, &c->status, (size_t)n))) return r;
@@ -289,6 +307,7 @@ int ensureWide(t4_ctx *c, int reads, int parts, int groups) {
   if (reads > w.maxReads) {
     int n = w.maxReads > 0 ? w.maxReads : 64;
     while (n < reads) n *= 2;
+    w.maxReads = 0;
     if ((r = devAlloc(c, &w.seed, 2 * (size_t)n * T4_WIDE_SEEDS))) return r;   // (two of everything: wideHalf)
     if ((r = devAlloc(c, &w.bounds, 2 * (size_t)n * (T4_WIDE_MAXP + 1)))) return r;
     if ((r = devAlloc(c, &w.uniqPref, 2 * (size_t)n * (w.pcap + 1)))) return r;
@@ -299,6 +318,7 @@ int ensureWide(t4_ctx *c, int reads, int parts, int groups) {
     int n = w.maxPart > 0 ? w.maxPart : wideEnv("T4_WIDE_PARTS", 1024);
     while (n < parts) n *= 2;
     const size_t n2 = 2 * (size_t)n;
+    w.maxPart = 0;
     if ((r = devAlloc(c, &w.pCnt, n2))) return r;
     if ((r = devAlloc(c, &w.pRead, n2))) return r;
     if ((r = devAlloc(c, &w.pKeys, n2 * w.pcap))) return r;
@@ -316,7 +336,7 @@ int ensureWide(t4_ctx *c, int reads, int parts, int groups) {
     int n = w.grpCap > 0 ? w.grpCap : wideEnv("T4_WIDE_GROUPS", 1 << 20);
     while (n < groups) n *= 2;
     if (c->grpPoolHost) (void)hipHostFree(c->grpPoolHost);
-    c->grpPoolHost = nullptr; w.grpPool = nullptr;
+    c->grpPoolHost = nullptr; w.grpPool = nullptr; w.grpCap = 0;
     HIPCHK(c, hipHostMalloc(&c->grpPoolHost, sizeof(T4Grp) * 2 * (size_t)n, hipHostMallocMapped));
     HIPCHK(c, hipHostGetDevicePointer((void **)&w.grpPool, c->grpPoolHost, 0));
     w.grpCap = n;
@@ -872,7 +892,7 @@ int t4_reads_upload_flags(t4_ctx *c, const char *bases, const int64_t *offsets, 
     if (l > T4_MAXL) return fail(c, T4_ERR_UNSUPPORTED, "read %lld is %lld bp; this engine takes reads up to %d bp", (long long)i, (long long)l, T4_MAXL);
     if (l > maxLen) maxLen = (int)l;
   }
-  t4_batch *b = new t4_batch();
+  std::unique_ptr<t4_batch, void (*)(t4_batch *)> b(new t4_batch(), t4_batch_destroy);   // (and its device buffers, on every way out but the last)
   b->ctx = c; b->n = n; b->maxLen = maxLen;
   b->wpk = (maxLen + 15) / 16; b->wnm = (maxLen + 31) / 32;
   if (b->wpk == 0) b->wpk = 1;
@@ -915,27 +935,23 @@ int t4_reads_upload_flags(t4_ctx *c, const char *bases, const int64_t *offsets, 
     const long long i = badRead.load();
     char bad = '?';
     for (int64_t j = offsets[i]; j < offsets[i + 1]; ++j) { const char ch = bases[j]; if (nucNum(ch) < 0 && ch != 'N' && !((flags & T4_READS_KMERS_ONLY) && ch >= 'A' && ch <= 'Z')) { bad = ch; break; } }
-    delete b;
     return fail(c, T4_ERR_UNSUPPORTED, "read %lld has base '%c' (alphabet is ACGTN)", i, bad);
   }
   int r;
-  // a HIP error below must not leak the batch and its device buffers
-  #define UPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { t4_batch_destroy(b); return fail(c, T4_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); } } while (0)
   // + 4 words: the packed k-mer extraction reads one word past a read's row (masked out), also for the last read
-  if ((r = devAlloc(c, &b->dPk, pk.size() + 4)) || (r = devAlloc(c, &b->dNm, nm.size() + 4)) || (r = devAlloc(c, &b->dLen, len.size()))) { t4_batch_destroy(b); return r; }
+  if ((r = devAlloc(c, &b->dPk, pk.size() + 4)) || (r = devAlloc(c, &b->dNm, nm.size() + 4)) || (r = devAlloc(c, &b->dLen, len.size()))) return r;
   if (n > 0) {
-    UPCHK(hipMemcpy(b->dPk, pk.data(), sizeof(unsigned) * pk.size(), hipMemcpyHostToDevice));
-    UPCHK(hipMemcpy(b->dNm, nm.data(), sizeof(unsigned) * nm.size(), hipMemcpyHostToDevice));
-    UPCHK(hipMemcpy(b->dLen, len.data(), sizeof(int) * len.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b->dPk, pk.data(), sizeof(unsigned) * pk.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b->dNm, nm.data(), sizeof(unsigned) * nm.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b->dLen, len.data(), sizeof(int) * len.size(), hipMemcpyHostToDevice));
   }
   if (barcode) {
-    if ((r = devAlloc(c, &b->dBarcode, (size_t)n))) { t4_batch_destroy(b); return r; }
-    if (n > 0) UPCHK(hipMemcpy(b->dBarcode, barcode, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    if ((r = devAlloc(c, &b->dBarcode, (size_t)n))) return r;
+    if (n > 0) HIPCHK(c, hipMemcpy(b->dBarcode, barcode, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
   }
-  #undef UPCHK
   b->view.pk = b->dPk; b->view.nm = b->dNm; b->view.len = b->dLen; b->view.barcode = b->dBarcode;
   b->view.wpk = b->wpk; b->view.wnm = b->wnm; b->view.n = n;
-  *out = b;
+  *out = b.release();
   return T4_OK;
 }
 
@@ -1042,6 +1058,7 @@ int runQuery(t4_index *ix, t4_batch *b, T4QueryArgs qa, bool useBarcode, bool no
 
 int ensureResult(t4_ctx *c, size_t records) {
   if (records <= c->resultCap) return T4_OK;
+  c->resultCap = 0;
   int r = devAlloc(c, &c->result, records);
   if (r) return r;
   c->resultCap = records;
@@ -1093,13 +1110,13 @@ int t4_hits(t4_index *ix, t4_batch *b, int strand, int allow_total_skip, int64_t
   int grid = c->cus * 2;
   if ((long long)grid > n) grid = (int)n;
   const int HCAP = 65536;
-  if (grid > c->hitsGrid) { if ((r = devAlloc(c, &c->hitsKeys, (size_t)grid * HCAP))) return r; c->hitsGrid = grid; }
+  if (grid > c->hitsGrid) { c->hitsGrid = 0; if ((r = devAlloc(c, &c->hitsKeys, (size_t)grid * HCAP))) return r; c->hitsGrid = grid; }
   if ((r = ensurePerCall(c, n))) return r;
-  long long *dOff = nullptr;
-  T4HitOut *dHits = nullptr;
-  if ((r = devAlloc(c, &dOff, (size_t)n + 1))) return r;
+  DevBuf<long long> dOff;
+  DevBuf<T4HitOut> dHits;
+  if ((r = dOff.alloc(c, (size_t)n + 1))) return r;
   HIPCHK(c, hipMemsetAsync(c->status, 0, sizeof(int) * (size_t)n, c->stream));
-  hipLaunchKernelGGL(t4k::hitsKernel, dim3(grid), dim3(64), 0, c->stream, ix->view, b->view, strand, allow_total_skip, 0, dOff,
+  launch(t4k::hitsKernel, grid, 64, c->stream, ix->view, b->view, strand, allow_total_skip, 0, dOff,
                      (T4HitOut *)nullptr, c->hitsKeys, HCAP, c->status);
   HIPCHK(c, hipGetLastError());
   std::vector<long long> off((size_t)n + 1);
@@ -1110,19 +1127,17 @@ int t4_hits(t4_index *ix, t4_batch *b, int strand, int allow_total_skip, int64_t
   for (long long i = 0; i <= n; ++i) hit_offsets[i] = off[i];
   std::vector<int> status((size_t)n);
   HIPCHK(c, hipMemcpy(status.data(), c->status, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-  for (long long i = 0; i < n; ++i) if (status[i]) { (void)hipFree(dOff); return fail(c, T4_ERR_UNSUPPORTED, "read %lld has more than %d hits", i, HCAP); }
+  for (long long i = 0; i < n; ++i) if (status[i]) return fail(c, T4_ERR_UNSUPPORTED, "read %lld has more than %d hits", i, HCAP);
   if (hits) {
-    if (hits_cap < off[n]) { (void)hipFree(dOff); return fail(c, T4_ERR_ARG, "hits_cap %lld < %lld", (long long)hits_cap, off[n]); }
-    if ((r = devAlloc(c, &dHits, (size_t)off[n]))) { (void)hipFree(dOff); return r; }
+    if (hits_cap < off[n]) return fail(c, T4_ERR_ARG, "hits_cap %lld < %lld", (long long)hits_cap, off[n]);
+    if ((r = dHits.alloc(c, (size_t)off[n]))) return r;
     HIPCHK(c, hipMemcpyAsync(dOff, off.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(t4k::hitsKernel, dim3(grid), dim3(64), 0, c->stream, ix->view, b->view, strand, allow_total_skip, 1, dOff,
+    launch(t4k::hitsKernel, grid, 64, c->stream, ix->view, b->view, strand, allow_total_skip, 1, dOff,
                        dHits, c->hitsKeys, HCAP, c->status);
     HIPCHK(c, hipGetLastError());
     if (off[n]) HIPCHK(c, hipMemcpyAsync(hits, dHits, sizeof(t4_hit) * (size_t)off[n], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(dHits);
   }
-  (void)hipFree(dOff);
   return T4_OK;
 }
 
@@ -1144,32 +1159,30 @@ int t4_gap_dp_align(t4_ctx *c, int kind, int impl, int n, const int64_t *t_off, 
   if (grid > c->cus * 4) grid = c->cus * 4;
   int r;
   if ((r = ensureScratch(c, grid * 64))) return r;
-  long long *dT = nullptr, *dP = nullptr;
-  char *dTc = nullptr, *dPc = nullptr;
-  T4PW *dTw = nullptr;
-  int *dOut = nullptr;
+  DevBuf<long long> dT, dP;
+  DevBuf<char> dTc, dPc;
+  DevBuf<T4PW> dTw;
+  DevBuf<int> dOut;
   size_t tn = (size_t)t_off[n], pn = (size_t)p_off[n];
-  if ((r = devAlloc(c, &dT, (size_t)n + 1)) || (r = devAlloc(c, &dP, (size_t)n + 1)) || (r = devAlloc(c, &dPc, pn + 16)) || (r = devAlloc(c, &dOut, (size_t)n * 4))) return r;
-  if (kind == 0) { if ((r = devAlloc(c, &dTc, tn + 16))) return r; HIPCHK(c, hipMemcpy(dTc, t_data, tn, hipMemcpyHostToDevice)); }
+  if ((r = dT.alloc(c, (size_t)n + 1)) || (r = dP.alloc(c, (size_t)n + 1)) || (r = dPc.alloc(c, pn + 16)) || (r = dOut.alloc(c, (size_t)n * 4))) return r;
+  if (kind == 0) { if ((r = dTc.alloc(c, tn + 16))) return r; HIPCHK(c, hipMemcpy(dTc, t_data, tn, hipMemcpyHostToDevice)); }
   else {   // _posWeight columns (4 x int32) -> predicate bytes
     std::vector<T4PW> wb(tn + 1, t4PwByte(0, 0, 0, 0));
     const int32_t *w4 = (const int32_t *)t_data;
     for (size_t i = 0; i < tn; ++i) wb[i] = t4PwByte(w4[4 * i], w4[4 * i + 1], w4[4 * i + 2], w4[4 * i + 3]);
-    if ((r = devAlloc(c, &dTw, tn + 16))) return r;
+    if ((r = dTw.alloc(c, tn + 16))) return r;
     HIPCHK(c, hipMemcpy(dTw, wb.data(), tn + 1, hipMemcpyHostToDevice));
   }
   HIPCHK(c, hipMemcpy(dT, t_off, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dP, p_off, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dPc, p_chars, pn, hipMemcpyHostToDevice));
-  signed char *dAl = nullptr;
-  if (align) { if ((r = devAlloc(c, &dAl, (size_t)n * align_stride))) return r; HIPCHK(c, hipMemsetAsync(dAl, 0xFF, (size_t)n * align_stride, c->stream)); }
-  hipLaunchKernelGGL(t4k::gapDpKernel, dim3(grid), dim3(64), 0, c->stream, kind, impl, n, dT, dP, dTc, dTw, dPc, dOut, c->dpRows, c->dpDir, dAl, align_stride);
+  DevBuf<signed char> dAl;
+  if (align) { if ((r = dAl.alloc(c, (size_t)n * align_stride))) return r; HIPCHK(c, hipMemsetAsync(dAl, 0xFF, (size_t)n * align_stride, c->stream)); }
+  launch(t4k::gapDpKernel, grid, 64, c->stream, kind, impl, n, dT, dP, dTc, dTw, dPc, dOut, c->dpRows, c->dpDir, dAl, align_stride);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out4, dOut, sizeof(int) * (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
   if (align) HIPCHK(c, hipMemcpyAsync(align, dAl, (size_t)n * align_stride, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  void *ptrs[] = {dT, dP, dTc, dPc, dTw, dOut, dAl};
-  for (void *q : ptrs) if (q) (void)hipFree(q);
   return T4_OK;
 }
 
@@ -1180,24 +1193,22 @@ int t4_mate_overlap(t4_ctx *c, int n, const int64_t *f_off, const char *f_chars,
   if (n == 0) return T4_OK;
   (void)hipSetDevice(c->device);
   int r;
-  long long *dF = nullptr, *dS = nullptr;
-  char *dFc = nullptr, *dSc = nullptr;
-  int *dMo = nullptr, *dOut = nullptr;
+  DevBuf<long long> dF, dS;
+  DevBuf<char> dFc, dSc;
+  DevBuf<int> dMo, dOut;
   const size_t fn = (size_t)f_off[n], sn = (size_t)s_off[n];
-  if ((r = devAlloc(c, &dF, (size_t)n + 1)) || (r = devAlloc(c, &dS, (size_t)n + 1)) || (r = devAlloc(c, &dFc, fn + 16)) ||
-      (r = devAlloc(c, &dSc, sn + 16)) || (r = devAlloc(c, &dMo, (size_t)n)) || (r = devAlloc(c, &dOut, (size_t)n * 3))) return r;
+  if ((r = dF.alloc(c, (size_t)n + 1)) || (r = dS.alloc(c, (size_t)n + 1)) || (r = dFc.alloc(c, fn + 16)) ||
+      (r = dSc.alloc(c, sn + 16)) || (r = dMo.alloc(c, (size_t)n)) || (r = dOut.alloc(c, (size_t)n * 3))) return r;
   HIPCHK(c, hipMemcpy(dF, f_off, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dS, s_off, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice));
   if (fn) HIPCHK(c, hipMemcpy(dFc, f_chars, fn, hipMemcpyHostToDevice));
   if (sn) HIPCHK(c, hipMemcpy(dSc, s_chars, sn, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dMo, min_overlap, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
   int grid = n < c->cus * 32 ? n : c->cus * 32;
-  hipLaunchKernelGGL(t4k::mateOverlapKernel, dim3(grid), dim3(64), 0, c->stream, n, dF, dFc, dS, dSc, dMo, check_tandem ? 1 : 0, dOut);
+  launch(t4k::mateOverlapKernel, grid, 64, c->stream, n, dF, dFc, dS, dSc, dMo, check_tandem ? 1 : 0, dOut);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out3, dOut, sizeof(int) * (size_t)n * 3, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  void *ptrs[] = {dF, dS, dFc, dSc, dMo, dOut};
-  for (void *q : ptrs) if (q) (void)hipFree(q);
   for (int i = 0; i < n; ++i) if (out3[3 * i] == -2) return fail(c, T4_ERR_UNSUPPORTED, "pair %d has a read longer than %d bp", i, T4_MAXL);
   return T4_OK;
 }
@@ -1214,32 +1225,28 @@ int t4_process_pairs(t4_ctx *c, int n, const int64_t *off1, const char *r1, cons
     if ((has_qual[i] & 2) && !q2) return fail(c, T4_ERR_ARG, "t4_process_pairs: pair %d says read 2 has qualities, q2 is null", i);
   }
   int r;
-  long long *dO1 = nullptr, *dO2 = nullptr, *dOo = nullptr;
-  char *dR1 = nullptr, *dQ1 = nullptr, *dR2 = nullptr, *dQ2 = nullptr, *dOr = nullptr, *dOq = nullptr;
-  unsigned char *dHq = nullptr;
-  int4 *dMeta = nullptr;
-  auto freeAll = [&] { void *ptrs[] = {dO1, dO2, dOo, dR1, dQ1, dR2, dQ2, dOr, dOq, dHq, dMeta}; for (void *q : ptrs) if (q) (void)hipFree(q); };
-  #define PPCHK(x) do { if ((x) != hipSuccess) { freeAll(); return fail(c, T4_ERR_HIP, "HIP error in t4_process_pairs: %s", hipGetErrorString(hipGetLastError())); } } while (0)
-  if ((r = devAlloc(c, &dO1, (size_t)n + 1)) || (r = devAlloc(c, &dO2, (size_t)n + 1)) || (r = devAlloc(c, &dOo, (size_t)n + 1)) ||
-      (r = devAlloc(c, &dR1, n1 + 16)) || (r = devAlloc(c, &dR2, n2 + 16)) || (r = devAlloc(c, &dOr, no + 16)) || (r = devAlloc(c, &dOq, no + 16)) ||
-      (r = devAlloc(c, &dHq, (size_t)n)) || (r = devAlloc(c, &dMeta, (size_t)n)) || (q1 && (r = devAlloc(c, &dQ1, n1 + 16))) || (q2 && (r = devAlloc(c, &dQ2, n2 + 16)))) { freeAll(); return r; }
-  PPCHK(hipMemcpyAsync(dO1, off1, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
-  PPCHK(hipMemcpyAsync(dO2, off2, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
-  PPCHK(hipMemcpyAsync(dOo, out_off, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
-  if (n1) PPCHK(hipMemcpyAsync(dR1, r1, n1, hipMemcpyHostToDevice, c->stream));
-  if (n2) PPCHK(hipMemcpyAsync(dR2, r2, n2, hipMemcpyHostToDevice, c->stream));
-  if (q1 && n1) PPCHK(hipMemcpyAsync(dQ1, q1, n1, hipMemcpyHostToDevice, c->stream));
-  if (q2 && n2) PPCHK(hipMemcpyAsync(dQ2, q2, n2, hipMemcpyHostToDevice, c->stream));
-  PPCHK(hipMemcpyAsync(dHq, has_qual, (size_t)n, hipMemcpyHostToDevice, c->stream));
+  DevBuf<long long> dO1, dO2, dOo;
+  DevBuf<char> dR1, dQ1, dR2, dQ2, dOr, dOq;
+  DevBuf<unsigned char> dHq;
+  DevBuf<int4> dMeta;
+  if ((r = dO1.alloc(c, (size_t)n + 1)) || (r = dO2.alloc(c, (size_t)n + 1)) || (r = dOo.alloc(c, (size_t)n + 1)) ||
+      (r = dR1.alloc(c, n1 + 16)) || (r = dR2.alloc(c, n2 + 16)) || (r = dOr.alloc(c, no + 16)) || (r = dOq.alloc(c, no + 16)) ||
+      (r = dHq.alloc(c, (size_t)n)) || (r = dMeta.alloc(c, (size_t)n)) || (q1 && (r = dQ1.alloc(c, n1 + 16))) || (q2 && (r = dQ2.alloc(c, n2 + 16)))) return r;
+  HIPCHK(c, hipMemcpyAsync(dO1, off1, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dO2, off2, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dOo, out_off, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
+  if (n1) HIPCHK(c, hipMemcpyAsync(dR1, r1, n1, hipMemcpyHostToDevice, c->stream));
+  if (n2) HIPCHK(c, hipMemcpyAsync(dR2, r2, n2, hipMemcpyHostToDevice, c->stream));
+  if (q1 && n1) HIPCHK(c, hipMemcpyAsync(dQ1, q1, n1, hipMemcpyHostToDevice, c->stream));
+  if (q2 && n2) HIPCHK(c, hipMemcpyAsync(dQ2, q2, n2, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dHq, has_qual, (size_t)n, hipMemcpyHostToDevice, c->stream));
   const int grid = n < c->cus * 32 ? n : c->cus * 32;
-  hipLaunchKernelGGL(t4k::processPairKernel, dim3(grid), dim3(64), 0, c->stream, n, dO1, dR1, dQ1, dO2, dR2, dQ2, dHq, dOo, dOr, dOq, dMeta);
-  PPCHK(hipGetLastError());
-  PPCHK(hipMemcpyAsync(meta4, dMeta, sizeof(int4) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  PPCHK(hipMemcpyAsync(out_r, dOr, no, hipMemcpyDeviceToHost, c->stream));
-  PPCHK(hipMemcpyAsync(out_q, dOq, no, hipMemcpyDeviceToHost, c->stream));
-  PPCHK(hipStreamSynchronize(c->stream));
-  #undef PPCHK
-  freeAll();
+  launch(t4k::processPairKernel, grid, 64, c->stream, n, dO1, dR1, dQ1, dO2, dR2, dQ2, dHq, dOo, dOr, dOq, dMeta);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(meta4, dMeta, sizeof(int4) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out_r, dOr, no, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out_q, dOq, no, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < n; ++i) if (meta4[4 * i] == -2) return fail(c, T4_ERR_UNSUPPORTED, "pair %d has a read longer than %d bp", i, T4_MAXL);
   return T4_OK;
 }
@@ -1378,17 +1385,16 @@ int t4_kmer_count_set(t4_kmer_counter *kc, const uint64_t *codes, const int32_t 
   const long long m = (long long)hc.size();
   int r;
   if ((r = kmerEnsureRoom(kc, (unsigned long long)m))) return r;
-  unsigned long long *dC = nullptr; int *dV = nullptr;
-  if ((r = devAlloc(c, &dC, (size_t)m)) || (r = devAlloc(c, &dV, (size_t)m))) return r;
+  DevBuf<unsigned long long> dC; DevBuf<int> dV;
+  if ((r = dC.alloc(c, (size_t)m)) || (r = dV.alloc(c, (size_t)m))) return r;
   HIPCHK(c, hipMemcpy(dC, hc.data(), sizeof(unsigned long long) * (size_t)m, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dV, hv.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice));
   const int grid = (int)((m + 255) / 256 < (long long)c->cus * 8 ? (m + 255) / 256 : (long long)c->cus * 8);
-  hipLaunchKernelGGL(t4k::kmerSetKernel, dim3(grid), dim3(256), 0, c->stream, kc->tb, (const unsigned long long *)dC, (const int *)dV, m);
+  launch(t4k::kmerSetKernel, grid, 256, c->stream, kc->tb, (const unsigned long long *)dC, (const int *)dV, m);
   HIPCHK(c, hipGetLastError());
   int overflow = 0;
   HIPCHK(c, hipMemcpyAsync(&overflow, kc->tb.overflow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(dC); (void)hipFree(dV);
   if (overflow) return fail(c, T4_ERR_UNSUPPORTED, "t4_kmer_count_set: more distinct k-mers than the table was created for (%llu slots)", kc->slots);
   return T4_OK;
 }
@@ -1403,13 +1409,12 @@ int t4_kmer_count_export(t4_kmer_counter *kc, uint64_t *codes, int32_t *counts, 
   *n_out = (int64_t)used;
   if (cap == 0 || used == 0) return T4_OK;
   int r;
-  unsigned long long *dC = nullptr, *dCur = nullptr; int *dV = nullptr;
-  struct Free { unsigned long long *&a, *&b; int *&v; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (v) (void)hipFree(v); } } freeOnReturn{dC, dCur, dV};   // (every path out of here)
-  if ((r = devAlloc(c, &dC, (size_t)cap)) || (r = devAlloc(c, &dV, (size_t)cap)) || (r = devAlloc(c, &dCur, (size_t)1))) return r;
+  DevBuf<unsigned long long> dC, dCur; DevBuf<int> dV;
+  if ((r = dC.alloc(c, (size_t)cap)) || (r = dV.alloc(c, (size_t)cap)) || (r = dCur.alloc(c, (size_t)1))) return r;
   HIPCHK(c, hipMemsetAsync(dCur, 0, sizeof(unsigned long long), c->stream));
   const unsigned long long blocks = (kc->slots + 255ull) / 256ull;
   const int grid = (int)(blocks < (unsigned long long)c->cus * 16ull ? blocks : (unsigned long long)c->cus * 16ull);
-  hipLaunchKernelGGL(t4k::kmerExportKernel, dim3(grid), dim3(256), 0, c->stream, kc->tb, dC, dV, dCur, (unsigned long long)cap);
+  launch(t4k::kmerExportKernel, grid, 256, c->stream, kc->tb, dC, dV, dCur, (unsigned long long)cap);
   HIPCHK(c, hipGetLastError());
   unsigned long long got = 0;
   HIPCHK(c, hipMemcpyAsync(&got, dCur, sizeof got, hipMemcpyDeviceToHost, c->stream));
@@ -1430,10 +1435,9 @@ int t4_kmer_count_merge(t4_kmer_counter *kc, const uint64_t *codes, const int32_
   (void)hipSetDevice(c->device);
   int r;
   const int64_t SLICE = (int64_t)1 << 26;   // pairs per upload (768 MB of device memory at most)
-  unsigned long long *dC = nullptr; int *dV = nullptr;
+  DevBuf<unsigned long long> dC; DevBuf<int> dV;
   const size_t cap = (size_t)(n < SLICE ? n : SLICE);
-  struct Free { unsigned long long *&a; int *&v; ~Free() { if (a) (void)hipFree(a); if (v) (void)hipFree(v); } } freeOnReturn{dC, dV};   // (every path out of here)
-  if ((r = devAlloc(c, &dC, cap)) || (r = devAlloc(c, &dV, cap))) return r;
+  if ((r = dC.alloc(c, cap)) || (r = dV.alloc(c, cap))) return r;
   int overflow = 0;
   for (int64_t lo = 0; lo < n && !overflow; lo += SLICE) {
     const int64_t m = n - lo < SLICE ? n - lo : SLICE;
@@ -1441,7 +1445,7 @@ int t4_kmer_count_merge(t4_kmer_counter *kc, const uint64_t *codes, const int32_
     HIPCHK(c, hipMemcpy(dC, codes + lo, sizeof(unsigned long long) * (size_t)m, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(dV, counts + lo, sizeof(int) * (size_t)m, hipMemcpyHostToDevice));
     const int grid = (int)((m + 255) / 256 < (long long)c->cus * 8 ? (m + 255) / 256 : (long long)c->cus * 8);
-    hipLaunchKernelGGL(t4k::kmerMergeKernel, dim3(grid), dim3(256), 0, c->stream, kc->tb, (const unsigned long long *)dC, (const int *)dV, (long long)m, only_present ? 1 : 0);
+    launch(t4k::kmerMergeKernel, grid, 256, c->stream, kc->tb, (const unsigned long long *)dC, (const int *)dV, (long long)m, only_present ? 1 : 0);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(&overflow, kc->tb.overflow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1460,29 +1464,27 @@ int t4_kmer_count_stats(t4_kmer_counter *kc, t4_batch *b, const char *quals, con
   if (kc->tb.perBarcode && !b->dBarcode) return fail(c, T4_ERR_ARG, "t4_kmer_count_stats: per-barcode counts need a batch uploaded with barcodes");
   (void)hipSetDevice(c->device);
   int r;
-  char *dQ = nullptr; long long *dOff = nullptr;
-  int *dMin = nullptr, *dMed = nullptr, *dLen = nullptr; float *dAvg = nullptr;
+  DevBuf<char> dQ; DevBuf<long long> dOff;
+  DevBuf<int> dMin, dMed, dLen; DevBuf<float> dAvg;
   if (quals) {
     std::vector<int> lens((size_t)n);
     HIPCHK(c, hipMemcpy(lens.data(), b->dLen, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
     for (long long i = 0; i < n; ++i)
       if (qual_off[i + 1] - qual_off[i] != lens[(size_t)i]) return fail(c, T4_ERR_ARG, "read %lld has %d bases and %lld qualities", i, lens[(size_t)i], (long long)(qual_off[i + 1] - qual_off[i]));
     const size_t qn = (size_t)qual_off[n];
-    if ((r = devAlloc(c, &dQ, qn + 16)) || (r = devAlloc(c, &dOff, (size_t)n + 1))) return r;
+    if ((r = dQ.alloc(c, qn + 16)) || (r = dOff.alloc(c, (size_t)n + 1))) return r;
     if (qn) HIPCHK(c, hipMemcpy(dQ, quals, qn, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(dOff, qual_off, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice));
   }
-  if ((r = devAlloc(c, &dMin, (size_t)n)) || (r = devAlloc(c, &dMed, (size_t)n)) || (r = devAlloc(c, &dLen, (size_t)n)) || (r = devAlloc(c, &dAvg, (size_t)n))) return r;
+  if ((r = dMin.alloc(c, (size_t)n)) || (r = dMed.alloc(c, (size_t)n)) || (r = dLen.alloc(c, (size_t)n)) || (r = dAvg.alloc(c, (size_t)n))) return r;
   const int grid = (int)(n < (long long)c->cus * 32 ? n : (long long)c->cus * 32);
-  hipLaunchKernelGGL(t4k::kmerStatsKernel, dim3(grid), dim3(64), 0, c->stream, b->view, kc->tb, (const char *)dQ, (const long long *)dOff, dMin, dMed, dAvg, dLen);
+  launch(t4k::kmerStatsKernel, grid, 64, c->stream, b->view, kc->tb, (const char *)dQ, (const long long *)dOff, dMin, dMed, dAvg, dLen);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(min_cnt, dMin, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(median_cnt, dMed, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(avg_cnt, dAvg, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(new_len, dLen, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  void *ptrs[] = {dQ, dOff, dMin, dMed, dLen, dAvg};
-  for (void *q : ptrs) if (q) (void)hipFree(q);
   return T4_OK;
 }
 
@@ -1523,7 +1525,6 @@ int t4_assign(t4_index *ix, t4_batch *b, int strand, int32_t *ret, t4_overlap *o
   if ((r = ensureResult(c, (size_t)b->n))) return r;
   T4QueryArgs qa;
   memset(&qa, 0, sizeof qa);
-  memset(&qa, 0, sizeof qa);
   qa.mode = 2; qa.strand = strand; qa.skipRepeats = 0; qa.maxPerRead = 1; qa.counts = nullptr; qa.out = c->result; qa.ret = c->counts;
   if ((r = runQuery(ix, b, qa, true))) return r;
   if (ret && b->n) HIPCHK(c, hipMemcpy(ret, c->counts, sizeof(int) * (size_t)b->n, hipMemcpyDeviceToHost));
@@ -1540,17 +1541,16 @@ int t4_assign_strands(t4_index *ix, t4_batch *b, const int32_t *strands, int32_t
   int r;
   if ((r = ensurePerCall(c, b->n))) return r;
   if ((r = ensureResult(c, (size_t)b->n))) return r;
-  int *dSt = nullptr;
-  if ((r = devAlloc(c, &dSt, (size_t)b->n))) return r;
+  DevBuf<int> dSt;
+  if ((r = dSt.alloc(c, (size_t)b->n))) return r;
   HIPCHK(c, hipMemcpy(dSt, strands, sizeof(int) * (size_t)b->n, hipMemcpyHostToDevice));
   T4QueryArgs qa;
   memset(&qa, 0, sizeof qa);
   qa.mode = 2; qa.strand = 0; qa.strandPerRead = dSt; qa.skipRepeats = 0; qa.maxPerRead = 1; qa.counts = nullptr; qa.out = c->result; qa.ret = c->counts;
-  r = runQuery(ix, b, qa, true);
-  if (r == T4_OK && ret) { if (hipMemcpy(ret, c->counts, sizeof(int) * (size_t)b->n, hipMemcpyDeviceToHost) != hipSuccess) r = fail(c, T4_ERR_HIP, "copy of the AssignRead return values failed"); }
-  if (r == T4_OK && out) { if (hipMemcpy(out, c->result, sizeof(t4_overlap) * (size_t)b->n, hipMemcpyDeviceToHost) != hipSuccess) r = fail(c, T4_ERR_HIP, "copy of the AssignRead results failed"); }
-  (void)hipFree(dSt);
-  return r;
+  if ((r = runQuery(ix, b, qa, true))) return r;
+  if (ret) HIPCHK(c, hipMemcpy(ret, c->counts, sizeof(int) * (size_t)b->n, hipMemcpyDeviceToHost));
+  if (out) HIPCHK(c, hipMemcpy(out, c->result, sizeof(t4_overlap) * (size_t)b->n, hipMemcpyDeviceToHost));
+  return T4_OK;
 }
 
 int t4_posweight_recompute(t4_index *ix, t4_batch *b, const t4_overlap *assign, const int32_t *mult, int32_t *posweight, int64_t posweight_cap) {
@@ -1572,50 +1572,48 @@ int t4_consensus_recompute(t4_index *ix, t4_batch *b, const t4_overlap *assign, 
   if (bases == 0) return T4_OK;
   (void)hipSetDevice(c->device);
   int r;
-  int *dCnt = nullptr, *dMult = nullptr;
-  T4OverlapOut *dAs = nullptr;
+  DevBuf<int> dCnt, dMult;
+  DevBuf<T4OverlapOut> dAs;
+  DevBuf<char> dCons;
+  DevBuf<unsigned long long> dChanged;
   const size_t n = (size_t)b->n;
   const size_t cols = (size_t)bases + ix->seqs.size();   // the image's column space: every contig is followed by one terminator column (T4SeqInfo::pwOff)
-  if ((r = devAlloc(c, &dCnt, cols * 4))) return r;
-  char *dCons = nullptr;
-  unsigned long long *dChanged = nullptr;
-  auto freeAll = [&] { if (dCnt) (void)hipFree(dCnt); if (dMult) (void)hipFree(dMult); if (dAs) (void)hipFree(dAs); if (dCons) (void)hipFree(dCons); if (dChanged) (void)hipFree(dChanged); };
-  #define PWCHK(x) do { if ((x) != hipSuccess) { freeAll(); return fail(c, T4_ERR_HIP, "HIP error in t4_posweight_recompute: %s", hipGetErrorString(hipGetLastError())); } } while (0)
-  PWCHK(hipMemsetAsync(dCnt, 0, sizeof(int) * cols * 4, c->stream));   // posWeight.SetZero of every contig
+  if ((r = dCnt.alloc(c, cols * 4))) return r;
+  HIPCHK(c, hipMemsetAsync(dCnt, 0, sizeof(int) * cols * 4, c->stream));   // posWeight.SetZero of every contig
   if (n > 0) {
-    if ((r = devAlloc(c, &dAs, n))) { freeAll(); return r; }
-    PWCHK(hipMemcpyAsync(dAs, assign, sizeof(t4_overlap) * n, hipMemcpyHostToDevice, c->stream));
+    if ((r = dAs.alloc(c, n))) return r;
+    HIPCHK(c, hipMemcpyAsync(dAs, assign, sizeof(t4_overlap) * n, hipMemcpyHostToDevice, c->stream));
     if (mult) {
-      if ((r = devAlloc(c, &dMult, n))) { freeAll(); return r; }
-      PWCHK(hipMemcpyAsync(dMult, mult, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+      if ((r = dMult.alloc(c, n))) return r;
+      HIPCHK(c, hipMemcpyAsync(dMult, mult, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
     }
     const int grid = (int)(n < (size_t)c->cus * 32 ? n : (size_t)c->cus * 32);
-    hipLaunchKernelGGL(t4k::posWeightAccumulateKernel, dim3(grid), dim3(64), 0, c->stream, ix->view, b->view, (const T4OverlapOut *)dAs, (const int *)dMult, dCnt);
-    PWCHK(hipGetLastError());
+    launch(t4k::posWeightAccumulateKernel, grid, 64, c->stream, ix->view, b->view, (const T4OverlapOut *)dAs, (const int *)dMult, dCnt);
+    HIPCHK(c, hipGetLastError());
   }
   {
     const int nseq = (int)ix->seqs.size();
     const int grid = nseq < c->cus * 8 ? nseq : c->cus * 8;
-    hipLaunchKernelGGL(t4k::posWeightFinishKernel, dim3(grid > 0 ? grid : 1), dim3(256), 0, c->stream, ix->view, dCnt);
-    PWCHK(hipGetLastError());
+    launch(t4k::posWeightFinishKernel, grid > 0 ? grid : 1, 256, c->stream, ix->view, dCnt);
+    HIPCHK(c, hipGetLastError());
   }
   std::vector<char> allCons;
   unsigned long long nChanged = 0;
   if (consensus) {   // UpdateConsensus of every contig from the columns just rebuilt
-    if ((r = devAlloc(c, &dCons, cols))) { freeAll(); return r; }
-    if ((r = devAlloc(c, &dChanged, 1))) { freeAll(); return r; }
-    PWCHK(hipMemsetAsync(dChanged, 0, sizeof(unsigned long long), c->stream));
+    if ((r = dCons.alloc(c, cols))) return r;
+    if ((r = dChanged.alloc(c, 1))) return r;
+    HIPCHK(c, hipMemsetAsync(dChanged, 0, sizeof(unsigned long long), c->stream));
     const int nseq = (int)ix->seqs.size();
     const int grid = nseq < c->cus * 8 ? nseq : c->cus * 8;
-    hipLaunchKernelGGL(t4k::consensusArgmaxKernel, dim3(grid > 0 ? grid : 1), dim3(256), 0, c->stream, ix->view, (const int *)dCnt, dCons, dChanged);
-    PWCHK(hipGetLastError());
+    launch(t4k::consensusArgmaxKernel, grid > 0 ? grid : 1, 256, c->stream, ix->view, (const int *)dCnt, dCons, dChanged);
+    HIPCHK(c, hipGetLastError());
     allCons.resize(cols);
-    PWCHK(hipMemcpyAsync(allCons.data(), dCons, cols, hipMemcpyDeviceToHost, c->stream));
-    PWCHK(hipMemcpyAsync(&nChanged, dChanged, sizeof nChanged, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(allCons.data(), dCons, cols, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&nChanged, dChanged, sizeof nChanged, hipMemcpyDeviceToHost, c->stream));
   }
   std::vector<int32_t> all(cols * 4);
-  PWCHK(hipMemcpyAsync(all.data(), dCnt, sizeof(int) * cols * 4, hipMemcpyDeviceToHost, c->stream));
-  PWCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(all.data(), dCnt, sizeof(int) * cols * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   if (changed) *changed = (int64_t)nChanged;
   {   // contig after contig, without the terminator columns
     size_t from = 0, to = 0;
@@ -1626,8 +1624,6 @@ int t4_consensus_recompute(t4_index *ix, t4_batch *b, const t4_overlap *assign, 
       from += ln + 1; to += ln;
     }
   }
-  #undef PWCHK
-  freeAll();
   return T4_OK;
 }
 
@@ -1643,23 +1639,19 @@ int t4_extend(t4_index *ix, t4_batch *b, int max_per_read, const int32_t *counts
   int r;
   if ((r = ensurePerCall(c, b->n))) return r;
   if ((r = ensureResult(c, m))) return r;
-  T4OverlapOut *dIn = nullptr;
-  int *dCnt = nullptr, *dRet = nullptr;
-  if ((r = devAlloc(c, &dIn, m)) || (r = devAlloc(c, &dCnt, n)) || (r = devAlloc(c, &dRet, m))) return r;
+  DevBuf<T4OverlapOut> dIn;
+  DevBuf<int> dCnt, dRet;
+  if ((r = dIn.alloc(c, m)) || (r = dCnt.alloc(c, n)) || (r = dRet.alloc(c, m))) return r;
   HIPCHK(c, hipMemcpy(dIn, in, sizeof(t4_overlap) * m, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dCnt, counts, sizeof(int) * n, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemset(dRet, 0, sizeof(int) * m));
   T4QueryArgs qa;
   memset(&qa, 0, sizeof qa);
-  memset(&qa, 0, sizeof qa);
   qa.mode = 3; qa.maxPerRead = max_per_read; qa.out = c->result; qa.in = dIn; qa.inCounts = dCnt; qa.ret = dRet; qa.mismatchFactor = mismatch_factor;
-  r = runQuery(ix, b, qa, true, true);
-  if (r == T4_OK) {
-    if (ret) HIPCHK(c, hipMemcpy(ret, dRet, sizeof(int) * m, hipMemcpyDeviceToHost));
-    if (out) HIPCHK(c, hipMemcpy(out, c->result, sizeof(t4_overlap) * m, hipMemcpyDeviceToHost));
-  }
-  (void)hipFree(dIn); (void)hipFree(dCnt); (void)hipFree(dRet);
-  return r;
+  if ((r = runQuery(ix, b, qa, true, true))) return r;
+  if (ret) HIPCHK(c, hipMemcpy(ret, dRet, sizeof(int) * m, hipMemcpyDeviceToHost));
+  if (out) HIPCHK(c, hipMemcpy(out, c->result, sizeof(t4_overlap) * m, hipMemcpyDeviceToHost));
+  return T4_OK;
 }
 
 }  // extern "C"

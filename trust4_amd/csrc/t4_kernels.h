@@ -4675,7 +4675,8 @@ __global__ __launch_bounds__(64) void processPairKernel(int n, const long long *
 
 // t4_gap_dp: a batch of independent gap alignments, one per lane. kind 0: AlignAlgo::GlobalAlignment on
 // chars, kind 1: GlobalAlignment_PosWeight on weights. impl 0: forward LDS version with scratch fallback
-// (what overlap scoring uses), impl 1: scratch + traceback version only. out: 3 ints per problem.
+// (dpAffineFwd / dpPosWeightFwd: this kernel alone calls them; overlap scoring runs the impl 2 and impl 3
+// formulations with the scratch-row aligner behind them), impl 1: scratch + traceback version only. out: 3 ints per problem.
 __global__ __launch_bounds__(64) void gapDpKernel(int kind, int impl, int n, const long long *tOff, const long long *pOff,
                                                  const char *tChars, const T4PW *tW, const char *pChars, int *out,
                                                  int *dpRows, unsigned char *dpDir, signed char *alignOut, int alignStride) {
