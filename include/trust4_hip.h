@@ -349,6 +349,11 @@ int t4_cellset_output(t4_cellset *cs, const char *path, const char *const *barco
 int t4_cellset_output_at(t4_cellset *cs, const char *path, const char *const *barcode_names, int n_names, int id_base, int append);
 int t4_cellset_counters(const t4_cellset *cs, int64_t *query_batches, int64_t *reads_queried, int64_t *images_staged,
                         int64_t *bytes_staged, double *sec_query, double *sec_stage);
+/* How the cells' device images were made. A cell's image travels without its hash table: the host ships one 16-byte record per
+ * key and everything behind the table, and the table is built in the cell's arena slot on the device. Up to 4 values, the first
+ * min(n, 4) of: images whose table was built on the device; key records shipped for them; table bytes written on the device
+ * (16 per slot, summed over those images); bytes staged over PCIe (== bytes_staged of t4_cellset_counters). */
+int t4_cellset_image_stats(const t4_cellset *cs, int64_t *out, int n);
 
 /* ---- k-mer counts of the read set ------------------------------------------------ */
 /* KmerCount (KmerCount.hpp): counts of the canonical k-mers of the reads (main.cpp:905-915 counts 21-mers of every read that

@@ -93,6 +93,7 @@ def _load():
         "t4_cellset_close_cell": (I, [P, P]), "t4_cellset_prefetch": (I, [P, I, P, P, P, I]),
         "t4_cellset_update_all_consensus": (I, [P]), "t4_cellset_set_threads": (I, [P, I]), "t4_cellset_size": (I, [P]),
         "t4_cellset_output": (I, [P, C.c_char_p, P, I]), "t4_cellset_counters": (I, [P, P, P, P, P, P, P]),
+        "t4_cellset_image_stats": (I, [P, P, I]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name) and os.environ.get("T4_LIB"):   # an older build of the library under T4_LIB (A/B timing of a kernel): the calls it lacks fail when made
@@ -397,6 +398,12 @@ class CellSet:
         self.eng.check(self.eng.lib.t4_cellset_counters(self.h, C.byref(q), C.byref(r), C.byref(i), C.byref(b), C.byref(sq), C.byref(ss)))
         return {"query_batches": q.value, "reads_queried": r.value, "images_staged": i.value, "bytes_staged": b.value,
                 "sec_query": sq.value, "sec_stage": ss.value}
+
+    def image_stats(self):
+        """how the cells' device images were made: tables built on the device from compact key records"""
+        v = (C.c_int64 * 4)()
+        self.eng.check(self.eng.lib.t4_cellset_image_stats(self.h, C.cast(v, C.c_void_p), 4))
+        return {"images_built_on_device": v[0], "key_records_shipped": v[1], "table_bytes_built_on_device": v[2], "bytes_staged": v[3]}
 
     def close(self):
         if getattr(self, "h", None):

@@ -2351,7 +2351,7 @@ struct t4_cellstore {
   t4_ctx *ctx = nullptr;
   int k = 9, hitLenRequired = 31, radius = 10, nomatchGapLimit = 0;
   double novelSim = 0.9;
-  struct Slot { unsigned char *base = nullptr; size_t cap = 0; bool live = false; bool pending = false; };
+  struct Slot { unsigned char *base = nullptr; size_t cap = 0, imgBytes = 0; bool live = false; bool pending = false; };
   std::vector<Slot> slots;
   std::vector<int> freeIds;
   std::vector<unsigned char *> chunks;
@@ -2363,7 +2363,12 @@ struct t4_cellstore {
   size_t stCap = 0, stUsed = 0;
   std::vector<T4CopyDesc> descs;
   T4CopyDesc *dDescs = nullptr;
-  size_t descCap = 0;
+  size_t descCap = 0;   // bytes: the descriptors of a flush and, behind them, its table builds travel in one copy
+  std::vector<T4TableBuild> builds;   // tables of the compact images of this flush (t4_cellstore_stage_compact)
+  std::vector<int> buildSlots;        // ... and the slot each belongs to, for the error text
+  std::vector<unsigned char> ctlHost;
+  int *dBuildErr = nullptr, *hBuildErr = nullptr;   // 0, or 1 + the number of a build that met a duplicate key (device word, pinned copy)
+  int64_t imagesBuilt = 0, keysShipped = 0, tableBytesBuilt = 0;
   std::vector<T4BytePatch> patches;
   T4BytePatch *dPatches = nullptr;
   size_t patchCap = 0;
@@ -2423,13 +2428,36 @@ int cellFlushPatches(t4_cellstore *cs) {
 int cellFlush(t4_cellstore *cs) {
   if (cs->descs.empty()) return cellFlushPatches(cs);
   t4_ctx *c = cs->ctx;
-  if (cs->descs.size() > cs->descCap) {
+  const size_t descBytes = (sizeof(T4CopyDesc) * cs->descs.size() + 15) & ~(size_t)15, buildBytes = sizeof(T4TableBuild) * cs->builds.size();
+  if (descBytes + buildBytes > cs->descCap) {
     if (cs->dDescs) { (void)hipStreamSynchronize(c->stream); (void)hipFree(cs->dDescs); cs->dDescs = nullptr; }
-    cs->descCap = cs->descs.size() * 2;
-    HIPCHK(c, hipMalloc(&cs->dDescs, sizeof(T4CopyDesc) * cs->descCap));
+    cs->descCap = (descBytes + buildBytes) * 2;
+    unsigned char *p = nullptr;
+    HIPCHK(c, hipMalloc(&p, cs->descCap));
+    cs->dDescs = (T4CopyDesc *)p;
+  }
+  const unsigned char *ctl = (const unsigned char *)cs->descs.data();
+  if (buildBytes) {
+    cs->ctlHost.resize(descBytes + buildBytes);
+    memcpy(cs->ctlHost.data(), cs->descs.data(), sizeof(T4CopyDesc) * cs->descs.size());
+    memcpy(cs->ctlHost.data() + descBytes, cs->builds.data(), buildBytes);
+    ctl = cs->ctlHost.data();
   }
   HIPCHK(c, hipMemcpyAsync(cs->stDev, cs->stHost, cs->stUsed, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(cs->dDescs, cs->descs.data(), sizeof(T4CopyDesc) * cs->descs.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(cs->dDescs, ctl, buildBytes ? descBytes + buildBytes : sizeof(T4CopyDesc) * cs->descs.size(), hipMemcpyHostToDevice, c->stream));
+  if (buildBytes) {   // the tables first, then the rest of the images: the two write disjoint bytes of a slot
+    if (!cs->hBuildErr) HIPCHK(c, hipHostMalloc(&cs->hBuildErr, sizeof(int), hipHostMallocDefault));
+    if (!cs->dBuildErr) {
+      HIPCHK(c, hipMalloc(&cs->dBuildErr, sizeof(int)));
+      HIPCHK(c, hipMemsetAsync(cs->dBuildErr, 0, sizeof(int), c->stream));
+    }
+    int bgrid = (int)cs->builds.size();
+    if (bgrid > c->cus * 8) bgrid = c->cus * 8;
+    hipLaunchKernelGGL(t4k::cellTableBuildKernel, dim3(bgrid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev,
+                       (const T4TableBuild *)((const unsigned char *)cs->dDescs + descBytes), (int)cs->builds.size(), cs->dBuildErr);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(cs->hBuildErr, cs->dBuildErr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  }
   int grid = (int)cs->descs.size();
   if (grid > c->cus * 8) grid = c->cus * 8;
   hipLaunchKernelGGL(t4k::scatterKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev, (const T4CopyDesc *)cs->dDescs, (int)cs->descs.size());
@@ -2437,8 +2465,23 @@ int cellFlush(t4_cellstore *cs) {
   // the pageable descriptor vector and the pinned staging are reused by the next stage() calls
   HIPCHK(c, hipStreamSynchronize(c->stream));
   cs->bytesStaged += (int64_t)cs->stUsed;
-  cs->descs.clear(); cs->stUsed = 0;
+  int badSlot = -1;
+  if (buildBytes) {
+    cs->imagesBuilt += (int64_t)cs->builds.size();
+    for (const T4TableBuild &tb : cs->builds) { cs->keysShipped += (int64_t)tb.nKeys; cs->tableBytesBuilt += (int64_t)(sizeof(T4HashEntC) * tb.tableSlots); }
+    const int e = *cs->hBuildErr;
+    if (e) {
+      badSlot = (e >= 1 && e <= (int)cs->buildSlots.size()) ? cs->buildSlots[e - 1] : -2;
+      (void)hipMemsetAsync(cs->dBuildErr, 0, sizeof(int), c->stream);
+      (void)hipStreamSynchronize(c->stream);
+    }
+  }
+  cs->descs.clear(); cs->builds.clear(); cs->buildSlots.clear(); cs->stUsed = 0;
   for (t4_cellstore::Slot &sl : cs->slots) sl.pending = false;
+  if (badSlot != -1) {   // the store goes on; that slot's table is incomplete until its cell is staged again
+    (void)cellFlushPatches(cs);
+    return fail(c, T4_ERR_ARG, "the key records of the image of slot %d hold the same code twice", badSlot);
+  }
   return cellFlushPatches(cs);
 }
 }  // namespace
@@ -2464,6 +2507,8 @@ void t4_cellstore_destroy(t4_cellstore *cs) {
   if (cs->stDev) (void)hipFree(cs->stDev);
   if (cs->stHost) (void)hipHostFree(cs->stHost);
   if (cs->dDescs) (void)hipFree(cs->dDescs);
+  if (cs->dBuildErr) (void)hipFree(cs->dBuildErr);
+  if (cs->hBuildErr) (void)hipHostFree(cs->hBuildErr);
   if (cs->dPatches) (void)hipFree(cs->dPatches);
   delete cs;
 }
@@ -2488,17 +2533,29 @@ int t4_cellstore_close(t4_cellstore *cs, int slot) {
   return T4_OK;
 }
 
-size_t t4_cellstore_image_bytes(int nseq, int64_t nkeys, int64_t npost, int64_t cons_bytes) {
+namespace {
+// staged bytes of one image: its table in full (tableSlots = the table's slots) or as compact key records (tableSlots = 0)
+size_t cellStagedBytes(size_t tableSlots, int nseq, int64_t nkeys, int64_t npost, int64_t cons_bytes) {
   auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  size_t sz = 64;
-  while (2 * sz < 3 * (size_t)nkeys + 2) sz <<= 1;   // load factor <= 2/3
   const size_t pwCount = (size_t)cons_bytes;   // one predicate byte per consensus byte incl. the terminators
-  const size_t oPost = al16(sizeof(T4HashEntC) * sz), oSeq = al16(oPost + sizeof(int2) * (size_t)npost),
+  const size_t oPost = sizeof(T4HashEntC) * (tableSlots ? tableSlots : (size_t)nkeys), oSeq = al16(oPost + sizeof(int2) * (size_t)npost),
                oPw = al16(oSeq + sizeof(T4SeqInfo) * (size_t)nseq), oCons = al16(oPw + sizeof(T4PW) * pwCount);
   return al16(oCons + (size_t)cons_bytes + 16) + al16(sizeof(T4IndexView));
 }
+}  // namespace
 
-// Serial step before a group of (possibly concurrent) t4_cellstore_stage calls: room for `bytes` more staged bytes and a
+// t4_cellstore_stage_compact: the key records of at most nkeys keys, the image from its postings on, the view
+size_t t4_cellstore_image_bytes(int nseq, int64_t nkeys, int64_t npost, int64_t cons_bytes) {
+  return cellStagedBytes(0, nseq, nkeys, npost, cons_bytes);
+}
+// t4_cellstore_stage: the whole image with its table, the view (never less than the compact form of the same cell)
+size_t t4_cellstore_full_image_bytes(int nseq, int64_t nkeys, int64_t npost, int64_t cons_bytes) {
+  size_t sz = 64;
+  while (2 * sz < 3 * (size_t)nkeys + 2) sz <<= 1;   // load factor <= 2/3
+  return cellStagedBytes(sz, nseq, nkeys, npost, cons_bytes);
+}
+
+// Serial step before a group of (possibly concurrent) t4_cellstore_stage / t4_cellstore_stage_compact calls: room for `bytes` more staged bytes and a
 // view entry for every slot id up to max_slot, so that no buffer moves while images are being written.
 int t4_cellstore_prepare(t4_cellstore *cs, int max_slot, size_t bytes) {
   if (!cs) return T4_ERR_ARG;
@@ -2521,16 +2578,22 @@ int t4_cellstore_prepare(t4_cellstore *cs, int max_slot, size_t bytes) {
   return cellStagingReserve(cs, bytes);
 }
 
-int t4_cellstore_stage(t4_cellstore *cs, int slot, int barcode, int nseq, const char *const *names, const char *const *cons,
-                       const int32_t *const *pw, int64_t nkeys64, const uint64_t *keyCode, const int32_t *keyBucket, const int32_t *keyCnt,
-                       const int32_t *postIn, int64_t *pwOffsetInImage, const int32_t *seqBarcodes) {
+}  // extern "C"
+
+namespace {
+// One cell's image into staging. compact: the table travels as the (code, start, cnt) records of its keys and is built in the slot
+// by cellTableBuildKernel; everything from the postings on is staged, and lands in the slot, as in the full form.
+int cellStage(t4_cellstore *cs, bool compact, int slot, int barcode, int nseq, const char *const *names, const char *const *cons,
+              const int32_t *const *pw, int64_t nkeys64, const uint64_t *keyCode, const int32_t *keyBucket, const int32_t *keyCnt,
+              const int32_t *postIn, int64_t *pwOffsetInImage, const int32_t *seqBarcodes) {
   if (!cs || slot < 0 || slot >= (int)cs->slots.size() || !cs->slots[slot].live || nseq < 0 || nkeys64 < 0) return T4_ERR_ARG;
   t4_ctx *c = cs->ctx;
   (void)hipSetDevice(c->device);
   if (nseq > T4_MAX_SEQS) return fail(c, T4_ERR_UNSUPPORTED, "more than %d sequences in one barcode", T4_MAX_SEQS);
   const size_t nkeys = (size_t)nkeys64;
   int64_t npost = 0;
-  for (size_t i = 0; i < nkeys; ++i) npost += keyCnt[i];
+  size_t nLive = 0;   // keys that own postings: the entries of the table
+  for (size_t i = 0; i < nkeys; ++i) { npost += keyCnt[i]; if (keyCnt[i] > 0) ++nLive; }
   size_t sz = 64;
   while (2 * sz < 3 * nkeys + 2) sz <<= 1;   // load factor <= 2/3
   size_t consBytes = 0, pwCount = 0;
@@ -2545,6 +2608,8 @@ int t4_cellstore_stage(t4_cellstore *cs, int slot, int barcode, int nseq, const 
                blobBytes = al16(oCons + consBytes + 16);
   int r;
   const size_t viewBytes = al16(sizeof(T4IndexView));
+  // staged: [key records | table] [oPost .. blobBytes of the image] [view]
+  const size_t headBytes = compact ? sizeof(T4HashEntC) * nLive : oPost, stagedBlob = headBytes + (blobBytes - oPost);
   unsigned char *b = nullptr, *slotBase = nullptr;
   size_t stOff = 0;
   {
@@ -2562,22 +2627,28 @@ int t4_cellstore_stage(t4_cellstore *cs, int slot, int barcode, int nseq, const 
       if ((r = cellAlloc(cs, cap, &p))) return r;
       sl.base = p; sl.cap = cap;
     }
-    slotBase = sl.base;
-    if (slot >= cs->viewCap || cs->stUsed + blobBytes + viewBytes > cs->stCap)
-      return fail(c, T4_ERR_STATE, "t4_cellstore_stage without a sufficient t4_cellstore_prepare (slot %d, %zu bytes)", slot, blobBytes + viewBytes);
+    slotBase = sl.base; sl.imgBytes = blobBytes;
+    if (slot >= cs->viewCap || cs->stUsed + stagedBlob + viewBytes > cs->stCap)
+      return fail(c, T4_ERR_STATE, "t4_cellstore_stage without a sufficient t4_cellstore_prepare (slot %d, %zu bytes)", slot, stagedBlob + viewBytes);
     stOff = cs->stUsed;
     b = cs->stHost + stOff;
     T4CopyDesc d0; d0.srcOff = stOff; d0.dst = slotBase; d0.bytes = blobBytes;
-    T4CopyDesc d1; d1.srcOff = stOff + blobBytes; d1.dst = (unsigned char *)(cs->dViews + slot); d1.bytes = viewBytes;
+    if (compact) {
+      d0.srcOff = stOff + headBytes; d0.dst = slotBase + oPost; d0.bytes = blobBytes - oPost;
+      T4TableBuild tb; tb.table = (T4HashEntC *)(slotBase + oHt); tb.tableSlots = sz; tb.srcOff = stOff; tb.nKeys = nLive;
+      cs->builds.push_back(tb); cs->buildSlots.push_back(slot);
+    }
+    T4CopyDesc d1; d1.srcOff = stOff + stagedBlob; d1.dst = (unsigned char *)(cs->dViews + slot); d1.bytes = viewBytes;
     cs->descs.push_back(d0); cs->descs.push_back(d1);
-    cs->stUsed += blobBytes + viewBytes;
+    cs->stUsed += stagedBlob + viewBytes;
   }
-  memset(b, 0, blobBytes + viewBytes);
-  T4HashEntC *ht = (T4HashEntC *)(b + oHt);
-  for (size_t t = 0; t < sz; ++t) ht[t].code = ~0ull;   // empty slots
-  int2 *post = (int2 *)(b + oPost);
+  memset(b, 0, stagedBlob + viewBytes);
+  T4HashEntC *ht = (T4HashEntC *)b;   // full: the table; compact: the key records, in the order of the keys
+  if (!compact) for (size_t t = 0; t < sz; ++t) ht[t].code = ~0ull;   // empty slots
+  unsigned char *tail = b + headBytes;   // the image from oPost on
+  int2 *post = (int2 *)tail;
   const unsigned long long hashMask = sz - 1;
-  size_t at = 0;
+  size_t at = 0, kAt = 0;
   for (size_t i = 0; i < nkeys; ++i) {
     const unsigned long long cd = keyCode[i];
     const int hb = keyBucket[i], cnt = keyCnt[i];
@@ -2588,14 +2659,17 @@ int t4_cellstore_stage(t4_cellstore *cs, int slot, int barcode, int nseq, const 
     }
     if (cnt <= 0) continue;
     if (hb != (int)((cd + (unsigned long long)(long long)(barcode + 1)) % 1000003ull)) return fail(c, T4_ERR_ARG, "key of another barcode in the image of barcode %d", barcode);
-    unsigned long long s = t4k::mix64(cd) & hashMask;
-    while (ht[s].code != ~0ull) s = (s + 1) & hashMask;
+    unsigned long long s = kAt++;
+    if (!compact) {
+      s = t4k::mix64(cd) & hashMask;
+      while (ht[s].code != ~0ull) s = (s + 1) & hashMask;
+    } else if (cd == ~0ull) return fail(c, T4_ERR_ARG, "key code ~0 marks an empty table slot");
     ht[s].code = cd; ht[s].start = (unsigned)at; ht[s].cnt = (unsigned)cnt;
     at += (size_t)cnt;
   }
-  T4SeqInfo *infos = (T4SeqInfo *)(b + oSeq);
-  T4PW *pwOut = (T4PW *)(b + oPw);
-  char *consOut = (char *)(b + oCons);
+  T4SeqInfo *infos = (T4SeqInfo *)(tail + (oSeq - oPost));
+  T4PW *pwOut = (T4PW *)(tail + (oPw - oPost));
+  char *consOut = (char *)(tail + (oCons - oPost));
   size_t consAt = 0, pwAt = 0;
   for (int i = 0; i < nseq; ++i) {
     T4SeqInfo &f = infos[i];
@@ -2614,7 +2688,7 @@ int t4_cellstore_stage(t4_cellstore *cs, int slot, int barcode, int nseq, const 
     pwAt += (size_t)l + 1;
   }
   if (pwOffsetInImage) *pwOffsetInImage = (int64_t)oPw;
-  T4IndexView &v = *(T4IndexView *)(b + blobBytes);
+  T4IndexView &v = *(T4IndexView *)(b + stagedBlob);
   v.k = cs->k; v.nseq = nseq; v.direct = 2; v.considerBarcode = 1;
   v.hashMask = hashMask; v.table = nullptr; v.htab = nullptr; v.ctab = (const T4HashEntC *)(slotBase + oHt); v.post = (const int2 *)(slotBase + oPost);
   v.seqs = (const T4SeqInfo *)(slotBase + oSeq); v.cons = (const char *)(slotBase + oCons); v.pw = (const T4PW *)(slotBase + oPw);
@@ -2622,6 +2696,43 @@ int t4_cellstore_stage(t4_cellstore *cs, int slot, int barcode, int nseq, const 
   v.firstIsRef = 0; v.hasNovel = 2;
   { int maxLen = 0; for (int i = 0; i < nseq; ++i) if (infos[i].len > maxLen) maxLen = infos[i].len; v.key32 = t4Key32Bits(nseq, maxLen); }
   v.novelSim = cs->novelSim; v.refSim = 0.75; v.repeatSim = 0.95;
+  return T4_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int t4_cellstore_stage(t4_cellstore *cs, int slot, int barcode, int nseq, const char *const *names, const char *const *cons,
+                       const int32_t *const *pw, int64_t nkeys, const uint64_t *keyCode, const int32_t *keyBucket, const int32_t *keyCnt,
+                       const int32_t *postIn, int64_t *pwOffsetInImage, const int32_t *seqBarcodes) {
+  return cellStage(cs, false, slot, barcode, nseq, names, cons, pw, nkeys, keyCode, keyBucket, keyCnt, postIn, pwOffsetInImage, seqBarcodes);
+}
+int t4_cellstore_stage_compact(t4_cellstore *cs, int slot, int barcode, int nseq, const char *const *names, const char *const *cons,
+                               const int32_t *const *pw, int64_t nkeys, const uint64_t *keyCode, const int32_t *keyBucket, const int32_t *keyCnt,
+                               const int32_t *postIn, int64_t *pwOffsetInImage, const int32_t *seqBarcodes) {
+  return cellStage(cs, true, slot, barcode, nseq, names, cons, pw, nkeys, keyCode, keyBucket, keyCnt, postIn, pwOffsetInImage, seqBarcodes);
+}
+
+// Test and diagnostic aid: flush, then the image of the slot as it lies in the arena (its table, postings, sequence records,
+// predicate bytes, consensus) and its view. *bytes is the image's size also when buf is null or cap too small (T4_ERR_ARG then).
+int t4_cellstore_read_image(t4_cellstore *cs, int slot, void *buf, size_t cap, size_t *bytes, void *view) {
+  if (!cs || slot < 0 || slot >= (int)cs->slots.size() || !bytes) return T4_ERR_ARG;
+  t4_ctx *c = cs->ctx;
+  (void)hipSetDevice(c->device);
+  int r;
+  if ((r = cellFlush(cs))) return r;
+  const t4_cellstore::Slot &sl = cs->slots[slot];
+  if (!sl.base || !sl.imgBytes || slot >= cs->viewCap) return fail(c, T4_ERR_STATE, "cell slot %d has no image", slot);
+  *bytes = sl.imgBytes;
+  if (buf && cap < sl.imgBytes) return fail(c, T4_ERR_ARG, "the image of slot %d has %zu bytes", slot, sl.imgBytes);
+  if (buf) HIPCHK(c, hipMemcpyAsync(buf, sl.base, sl.imgBytes, hipMemcpyDeviceToHost, c->stream));
+  if (view) HIPCHK(c, hipMemcpyAsync(view, cs->dViews + slot, sizeof(T4IndexView), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return T4_OK;
+}
+int t4_cellstore_image_stats(const t4_cellstore *cs, int64_t *out4) {
+  if (!cs || !out4) return T4_ERR_ARG;
+  out4[0] = cs->imagesBuilt; out4[1] = cs->keysShipped; out4[2] = cs->tableBytesBuilt; out4[3] = cs->bytesStaged + cs->bytesPatched;
   return T4_OK;
 }
 

@@ -1450,7 +1450,7 @@ struct t4_cellset {
   double novelSim = 0.9;
   std::map<int, t4_assembler *> cells;   // by barcode id == the reference's processing order of the cells
   int64_t queries = 0, readsQueried = 0, batchSeq = 0;
-  std::atomic<int64_t> stagedImages{0};
+  std::atomic<int64_t> stagedImages{0}, stagedLiveKeys{0};   // images handed to the store; keys with postings over those images, counted here
   double secQuery = 0, secStage = 0;
   int threads = 1;   // host threads for image builds and window bookkeeping (cells are independent)
   std::unique_ptr<t4_overlap[]> resOv, resEx;
@@ -1476,19 +1476,22 @@ int t4_assembler::stageImage() {   // thread-safe across cells once the owner ha
   // one list per (code, bucket) key, postings in the replica's order; the order of the keys does not matter to a hash table
   static thread_local std::vector<uint64_t> keyCode; static thread_local std::vector<int32_t> keyBucket, keyCnt, post;
   keyCode.clear(); keyBucket.clear(); keyCnt.clear(); post.clear();
+  int64_t liveKeys = 0;
   for (const auto &kv : index.map) {
+    if (kv.second.cnt) ++liveKeys;
     keyCode.push_back(kv.first.code); keyBucket.push_back(kv.first.h); keyCnt.push_back((int32_t)kv.second.cnt);
     for (uint32_t t = 0; t < kv.second.cnt; ++t) { const Post &p = index.arena[kv.second.start + t]; post.push_back(p.idx); post.push_back(p.offset); }
   }
   int64_t oPw = 0;
-  r = t4_cellstore_stage(owner->store, slot, cellBarcode, n, names.data(), cons.data(), pw.data(), (int64_t)keyCode.size(), keyCode.data(),
-                         keyBucket.data(), keyCnt.data(), post.data(), &oPw, nullptr);
+  r = t4_cellstore_stage_compact(owner->store, slot, cellBarcode, n, names.data(), cons.data(), pw.data(), (int64_t)keyCode.size(), keyCode.data(),
+                                 keyBucket.data(), keyCnt.data(), post.data(), &oPw, nullptr);
   if (r) return r;
   imgPwOff.resize(n);
   for (int i = 0; i < n; ++i) { imgPwOff[i] = oPw; oPw += (int64_t)strlen(cons[i]) + 1; }
   patches.clear();
   dirty = false; ++refreshes;
   ++owner->stagedImages;
+  owner->stagedLiveKeys += liveKeys;
   return T4_OK;
 }
 
@@ -3341,6 +3344,15 @@ int t4_cellset_counters(const t4_cellset *cs, int64_t *query_batches, int64_t *r
   if (bytes_staged) *bytes_staged = t4_cellstore_bytes_staged(cs->store);
   if (sec_query) *sec_query = cs->secQuery;
   if (sec_stage) *sec_stage = cs->secStage;
+  return T4_OK;
+}
+int64_t t4_cellset_live_keys_staged(const t4_cellset *cs) { return cs ? cs->stagedLiveKeys.load() : 0; }
+int t4_cellset_image_stats(const t4_cellset *cs, int64_t *out, int n) {
+  if (!cs || !out || n < 0) return T4_ERR_ARG;
+  int64_t v[4];
+  int r = t4_cellstore_image_stats(cs->store, v);
+  if (r) return r;
+  for (int i = 0; i < n && i < 4; ++i) out[i] = v[i];
   return T4_OK;
 }
 

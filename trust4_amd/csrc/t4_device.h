@@ -247,3 +247,4 @@ struct T4QueryArgs {
 
 struct T4BytePatch { unsigned char *dst; unsigned long long val; };   // one posWeight predicate byte of a resident image
 struct T4CopyDesc { unsigned long long srcOff; unsigned char *dst; unsigned long long bytes; };  // scatter of staged set images
+struct T4TableBuild { T4HashEntC *table; unsigned long long tableSlots, srcOff, nKeys; };   // table of a set image built on the device from nKeys staged (code, start, cnt) records

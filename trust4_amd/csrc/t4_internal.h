@@ -24,12 +24,21 @@ int t4_cellstore_stage(t4_cellstore *cs, int slot, int barcode, int nseq, const 
                        const int32_t *const *pw, int64_t nkeys, const uint64_t *key_code, const int32_t *key_bucket,
                        const int32_t *key_cnt, const int32_t *post, int64_t *pw_offset_in_image,
                        const int32_t *seq_barcodes /* nullable: per-sequence barcodes of a set that is not keyed by barcode */);
+// The same image with its table built on the device: staging receives the (code, start, cnt) records of the keys that own
+// postings, the image from its postings on and the view -- none of the table's empty slots. The flush writes the table's
+// slots empty in the arena and inserts the records there (cellTableBuildKernel); lookups see the same map. The same code
+// twice in key_code is refused by the flush (T4_ERR_ARG) and leaves that slot's table incomplete.
+int t4_cellstore_stage_compact(t4_cellstore *cs, int slot, int barcode, int nseq, const char *const *names, const char *const *cons,
+                               const int32_t *const *pw, int64_t nkeys, const uint64_t *key_code, const int32_t *key_bucket,
+                               const int32_t *key_cnt, const int32_t *post, int64_t *pw_offset_in_image, const int32_t *seq_barcodes);
 // Overwrite posWeight predicate bytes of the slot's resident image (byte offsets as returned by the last stage + the
 // column's index); applied after the staged images of the same flush.
 int t4_cellstore_patch(t4_cellstore *cs, int slot, int n, const int64_t *byte_offsets, const unsigned char *values);
-// Exact staged size of one image, and the serial reservation that must precede a group of t4_cellstore_stage calls
-// (which may then run concurrently on several host threads: nothing moves while they write).
+// Staged size of one image -- t4_cellstore_image_bytes: by t4_cellstore_stage_compact (exact when every key owns postings,
+// an upper bound otherwise); t4_cellstore_full_image_bytes: by t4_cellstore_stage, exact -- and the serial reservation that
+// must precede a group of stage calls (which may then run concurrently on several host threads: nothing moves while they write).
 size_t t4_cellstore_image_bytes(int nseq, int64_t nkeys, int64_t npost, int64_t cons_bytes);
+size_t t4_cellstore_full_image_bytes(int nseq, int64_t nkeys, int64_t npost, int64_t cons_bytes);
 int t4_cellstore_prepare(t4_cellstore *cs, int max_slot, size_t bytes);
 // Flush the staged images, then run the AddRead query (== t4_add_query) of read i against the image of slot[i].
 int t4_cellstore_query(t4_cellstore *cs, int n, const int32_t *slots, const char *bases, const int64_t *offsets,
@@ -37,6 +46,15 @@ int t4_cellstore_query(t4_cellstore *cs, int n, const int32_t *slots, const char
                        int max_per_read, int32_t *counts, t4_overlap *ov, t4_overlap *ext, int32_t *ext_ret);
 int t4_cellstore_set_big_first(t4_cellstore *cs, int on);   // first launch on the 8192-hit tier (one big set) instead of the 1024-hit tier
 int64_t t4_cellstore_bytes_staged(const t4_cellstore *cs);
+// 4 values: images whose table was built on the device, key records shipped for them, table bytes written on the device
+// (16 per slot), bytes staged over PCIe (== t4_cellstore_bytes_staged)
+int t4_cellstore_image_stats(const t4_cellstore *cs, int64_t *out4);
+// The host's own count of the keys with postings over all images a t4_cellset has staged: what value 1 of
+// t4_cellset_image_stats (key records the device builds were given) must equal.
+int64_t t4_cellset_live_keys_staged(const t4_cellset *cs);
+// Test and diagnostic aid: flushes, synchronises and copies the slot's image (table first) and its view (128 bytes) to
+// the host. *bytes receives the image's size; buf may be null to ask for it.
+int t4_cellstore_read_image(t4_cellstore *cs, int slot, void *buf, size_t cap, size_t *bytes, void *view);
 
 // t4_add_query with variable-size results (a read may overlap thousands of contigs that share a gene segment): counts[i]
 // records of read i start at index base[i] of ov / ext / ext_ret, which point into pinned memory of the ctx that stays

@@ -4183,6 +4183,37 @@ __global__ __launch_bounds__(256) void scatterKernel(const unsigned char *stagin
   }
 }
 
+// The open-addressing tables of freshly staged per-barcode set images, built where they live: image b's table gets every slot
+// written empty (code == ~0), then the image's compact key records (code, start, cnt) -- staged without the empty slots -- are
+// inserted by linear probing from mix64(code) & mask. One workgroup per image, one key per thread at a time; a slot is claimed by a
+// compare-and-swap of its code, so the order the keys land in differs from a serial build but a lookup, which probes from the home
+// slot to the first empty one, finds the same entry. A key whose code the table already holds (a duplicate) or that probes all the
+// way round writes the image's number + 1 to *err and gives up: the probe count is bounded by the table.
+__global__ __launch_bounds__(256) void cellTableBuildKernel(const unsigned char *staging, const T4TableBuild *build, int nBuild, int *err) {
+  for (int b = blockIdx.x; b < nBuild; b += gridDim.x) {
+    const T4TableBuild tb = build[b];
+    uint4 empty; empty.x = ~0u; empty.y = ~0u; empty.z = 0u; empty.w = 0u;
+    uint4 *slots = (uint4 *)tb.table;
+    for (unsigned long long i = threadIdx.x; i < tb.tableSlots; i += blockDim.x) slots[i] = empty;
+    __threadfence();   // the plain stores are in memory before another wave's atomic meets the slot
+    __syncthreads();
+    const T4HashEntC *keys = (const T4HashEntC *)(staging + tb.srcOff);
+    const unsigned long long mask = tb.tableSlots - 1;
+    for (unsigned long long k = threadIdx.x; k < tb.nKeys; k += blockDim.x) {
+      const T4HashEntC key = keys[k];
+      unsigned long long s = mix64(key.code) & mask, probes = 0;
+      bool placed = false;
+      for (; probes < tb.tableSlots; ++probes) {
+        const unsigned long long seen = atomicCAS(&tb.table[s].code, ~0ull, key.code);
+        if (seen == ~0ull) { *(uint2 *)&tb.table[s].start = make_uint2(key.start, key.cnt); placed = true; break; }
+        if (seen == key.code) break;   // the same code twice
+        s = (s + 1) & mask;
+      }
+      if (!placed) *err = b + 1;
+    }
+  }
+}
+
 // Patches of a live set's image (t4_index_apply_delta): run d copies bytes staging[srcOff ..) -> dst, one wavefront per run.
 // Runs never overlap (every destination is written once per delta).
 __global__ __launch_bounds__(256) void deltaKernel(const unsigned char *staging, const T4CopyDesc *desc, int nDesc) {

@@ -1793,11 +1793,14 @@ int main(int argc, char *argv[]) {
   auto cellSlots = [&]() { int n = 0; for (t4_cellset *cs : cellSets) n += t4_cellset_size(cs); return n; };
   auto destroyCells = [&]() { for (size_t g = 0; g < cellSets.size(); ++g) { t4_cellset_destroy(cellSets[g]); if (g > 0) t4_destroy(cellCtxs[g]); } cellSets.clear(); };
   auto writeCellStats = [&]() {
-    int64_t qb = 0, rq = 0, im = 0, by = 0; double sq = 0, ss = 0;
+    int64_t qb = 0, rq = 0, im = 0, by = 0, built = 0, keyRecs = 0, tabBytes = 0; double sq = 0, ss = 0;
     for (t4_cellset *cs : cellSets) {   // counts: sums over the cell groups; seconds: sums too (the groups overlap in time)
       int64_t a = 0, b = 0, c = 0, d = 0; double e = 0, f = 0;
       t4_cellset_counters(cs, &a, &b, &c, &d, &e, &f);
       qb += a; rq += b; im += c; by += d; sq += e; ss += f;
+      int64_t is[4] = {0, 0, 0, 0};
+      t4_cellset_image_stats(cs, is, 4);
+      built += is[0]; keyRecs += is[1]; tabBytes += is[2];
     }
     if (const char *sj = getenv("T4_STATS_JSON")) {
       FILE *fp = fopen(sj, "w");
@@ -1805,8 +1808,9 @@ int main(int argc, char *argv[]) {
         fprintf(fp, "{\"reads\": %d, \"threads\": %d, \"phases_s\": {", readCnt, threadCnt);
         for (size_t i = 0; i < phaseMarks.size(); ++i) fprintf(fp, "%s\"%s\": %.4f", i ? ", " : "", phaseMarks[i].first.c_str(), phaseMarks[i].second);
         fprintf(fp, "}, \"rough_annotation\": {\"reads\": %lld, \"hits\": %lld, \"kernel_ms\": %.3f}, ", annotReads, annotHits, annotKernelMs);
-        fprintf(fp, "\"cells\": {\"groups\": %d, \"query_batches\": %lld, \"reads_queried\": %lld, \"images_staged\": %lld, \"bytes_staged\": %lld, \"query_wall_s\": %.3f, \"stage_wall_s\": %.3f}, ",
-                (int)cellSets.size(), (long long)qb, (long long)rq, (long long)im, (long long)by, sq, ss);
+        fprintf(fp, "\"cells\": {\"groups\": %d, \"query_batches\": %lld, \"reads_queried\": %lld, \"images_staged\": %lld, \"bytes_staged\": %lld, \"query_wall_s\": %.3f, \"stage_wall_s\": %.3f, "
+                    "\"images_built_on_device\": %lld, \"key_records_shipped\": %lld, \"table_bytes_built_on_device\": %lld}, ",
+                (int)cellSets.size(), (long long)qb, (long long)rq, (long long)im, (long long)by, sq, ss, (long long)built, (long long)keyRecs, (long long)tabBytes);
         fprintf(fp, "\"contigs\": %d, \"assembled_reads\": %d}\n", cellSlots(), (int)assembledReadIdx.size());
         fclose(fp);
       }
