@@ -165,6 +165,20 @@ int t4_assign(t4_index *ix, t4_batch *b, int strand, int32_t *ret, t4_overlap *o
  * with the strand its AddRead settled on (main.cpp:2075-2116, AssignReads_Thread 607-626). */
 int t4_assign_strands(t4_index *ix, t4_batch *b, const int32_t *strands, int32_t *ret, t4_overlap *out);
 
+/* AssignRead without the limits of the single-workgroup tiers: a superset of the two entries above (strands == NULL: `strand` for every
+ * read, as t4_assign; else every read's own, as t4_assign_strands; ret / out laid out as there, either may be NULL). Every read
+ * those entries answer gets their bytes, -1 rows included. A read they refuse (a posting list beyond 10 000 entries, more than
+ * 262 144 hits, more than 16 384 overlaps) is answered like the reference: GetOverlapsFromRead(read, strand, barcode, 0, false) and
+ * the ExtendOverlap of every overlap (factor 1.0, with a barcode 2.0) run on the path of t4_add_query, which has the wide query
+ * behind it, and AssignRead's pick over its records runs on the device. A read that path refuses too keeps the refusal, with that
+ * path's message (the hits of one contig overflowing a partition, an overhang beyond the direction buffer; a read WITH a barcode
+ * stays off the wide query, so one that meets more than 10 000 postings in one (k-mer, barcode) list is still refused). Fails with
+ * T4_ERR_STATE while an AddRead query is in flight on the ctx (t4_assembler's windows use the same pools). Contig sets only.
+ * T4_ASSIGN_WIDE_ALL (environment, testing aid, read once per call): every read takes the second path; no result changes.
+ * t4_assign_wide_stats: of the last call on the ctx, out2[0] = reads the tiers answered, out2[1] = reads answered the other way. */
+int t4_assign_wide(t4_index *ix, t4_batch *b, int strand, const int32_t *strands, int32_t *ret, t4_overlap *out);
+int t4_assign_wide_stats(t4_ctx *ctx, int64_t *out2);
+
 /* SeqSet::RecomputePosWeight (SeqSet.hpp:4705-4738; main.cpp:2118) on a committed contig set: every posWeight column is zeroed,
  * every read with assign[i].seqIdx != -1 adds mult[i] (NULL: 1) to the column of each of its non-N bases on the strand
  * assign[i].strand from column assign[i].seqStart on (UpdatePosWeightFromRead, SeqSet.hpp:2466-2474), and columns no read covers

@@ -8,7 +8,7 @@
 //   main.cpp:1583-1940  seqSet.AddRead / RepeatAddRead / InputNovelRead / ...      -> t4bind::SeqSetProxy    (t4_assembler_*)
 //   main.cpp:2075-2118  extendedSeq.AssignRead of every assembled read,
 //                       extendedSeq.RecomputePosWeight                              -> t4bind::AssignReads, t4bind::RecomputePosWeight
-//                                                                                      (t4_assign_strands, t4_posweight_recompute)
+//                                                                                      (t4_assign_wide, t4_posweight_recompute)
 // integration/make_dropin.py applies the seven one-line edits (listed there) to a COPY of /root/reference/main.cpp at build time
 // and compiles it against this header; the result (oracle/_ref/trust4-dropin) is integration-test infrastructure: it proves the
 // boundary on the reference's own driver, `_final.out` included (tests/test_run_trust4_dropin.py). No reference source is stored
@@ -292,7 +292,9 @@ bool AssignReads(SeqSet &extendedSeq, AReads &assembledReads, int assembledReadC
   Check(t4_reads_upload(Ctx(), bases.data(), off.data(), NULL, n, &t.batch), "t4_reads_upload");
   t.assign.resize(n > 0 ? n : 1);
   std::vector<int32_t> ret(n > 0 ? n : 1);
-  if (n > 0) Check(t4_assign_strands(t.ix, t.batch, strands.data(), ret.data(), t.assign.data()), "t4_assign_strands");
+  // (t4_assign_wide: a read beyond the single-workgroup limits of t4_assign_strands -- a list of more than 10 000 postings on a deep sample -- is
+  // answered through the AddRead query path instead of ending the run)
+  if (n > 0) Check(t4_assign_wide(t.ix, t.batch, 0, strands.data(), ret.data(), t.assign.data()), "t4_assign_wide");
   // `assign` is one variable across the loop (main.cpp:2050): a failed AssignRead only sets seqIdx = -1 (SeqSet.hpp:4641) and leaves
   // the other fields of the last success behind
   struct _overlap assign;

@@ -75,6 +75,7 @@ def _load():
         "t4_mate_overlap": (I, [P, I, P, P, P, P, P, I, P]), "t4_has_hit": (I, [P, P, I, P]),
         "t4_process_pairs": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P]),
         "t4_extend": (I, [P, P, I, P, P, C.c_double, P, P]), "t4_assign": (I, [P, P, I, P, P]), "t4_assign_strands": (I, [P, P, P, P, P]),
+        "t4_assign_wide": (I, [P, P, I, P, P, P]), "t4_assign_wide_stats": (I, [P, P]),
         "t4_posweight_recompute": (I, [P, P, P, P, P, C.c_int64]),
         "t4_consensus_recompute": (I, [P, P, P, P, P, C.c_int64, P, C.c_int64, P]),
         "t4_assembler_create": (I, [P, I, I, C.POINTER(P)]), "t4_assembler_destroy": (None, [P]),
@@ -198,6 +199,12 @@ class Engine:
                 rd = r1[i]; ql = q1[i].encode("latin-1") if q1 is not None else bytes(ln)
             res.append((kind, rd, ql, fl & 15))
         return res
+
+    def assign_wide_stats(self):
+        """last assign_wide call on this engine -> (reads answered by the single-workgroup tiers, reads answered by the wide route)"""
+        out = (C.c_int64 * 2)()
+        self.check(self.lib.t4_assign_wide_stats(self.h, out))
+        return int(out[0]), int(out[1])
 
     def index(self, k, consider_barcode=False):
         return Index(self, k, consider_barcode)
@@ -535,6 +542,17 @@ class Index:
         ret = np.zeros(batch.n, dtype=np.int32)
         out = np.zeros(batch.n, dtype=OV_DTYPE)
         self.eng.check(self.eng.lib.t4_assign_strands(self.h, batch.h, st.ctypes.data_as(C.c_void_p), ret.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return ret, out
+
+    def assign_wide(self, batch, strand=0, strands=None):
+        """t4_assign_wide: assign / assign_strands without the single-workgroup limits -- reads beyond them are answered through the
+        AddRead query path and its wide query (strands: every read's own strand argument; None: `strand` for all)
+        -> (ret int32 [n], out OV_DTYPE [n])"""
+        st = None if strands is None else np.ascontiguousarray(strands, dtype=np.int32)
+        ret = np.zeros(batch.n, dtype=np.int32)
+        out = np.zeros(batch.n, dtype=OV_DTYPE)
+        self.eng.check(self.eng.lib.t4_assign_wide(self.h, batch.h, strand, None if st is None else st.ctypes.data_as(C.c_void_p),
+                                                   ret.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
         return ret, out
 
     def posweight_recompute(self, batch, assign, total_bases, mult=None):

@@ -73,6 +73,7 @@ struct AqCall {
   std::vector<unsigned char> allGlobal;
   size_t oPk, oNm, oLen, oBc, oSt, oLs, oVw, oFa, oOnly, oForce, oCs, oWide, oWideA, inBytes, pCb, pCc, pS8, pCnt, pSta, pNext, pNext2, pBase, pTick, pStab, pAux, pN4, pTail, pWctl, pWplan, pWstat, pWctlA, pWplanA, pWstatA, outBytes;
   bool hasOnly = false, hasForce = false, wantCands = false;
+  bool keepExtAux = false;   // t4_assign_wide: one word per pool record beside the public records (T4CandArgs::extAux)
   bool extendLater = false, wide = false, onlyRestricted = false;
   bool lazyDone = false, lazyStage = false;   // the wide pipeline behind the query kernel is launched only once the kernel is known to have deferred a read (aqEnd)
   int wideSafety = 32;   // of sixteenths: partitions are planned for half of their capacity
@@ -122,6 +123,9 @@ struct t4_ctx {
   T4OverlapOut *aqRecDev = nullptr;   // device copy of the overlap records + the read of each, for the extension launch
   int *aqRecRead = nullptr;
   int aqRecCap = 0;
+  int *aqExtAux = nullptr;   // T4CandArgs::extAux of the calls t4_assign_wide makes: one word per record of the result pool
+  int aqExtAuxCap = 0;
+  int64_t assignWide[2] = {0, 0};   // last t4_assign_wide call: reads answered by the single-workgroup tiers, reads answered by the wide route
   int64_t aqCalls = 0, aqReads = 0, aqGlobalLaunches = 0, aqGlobalReads = 0, aqRecords = 0;
   double aqSecPack = 0, aqSecFirst = 0, aqSecGlobal = 0;
   double aqSecLaunch[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // host seconds inside aqLaunch: preparation, prologue, second stream, query kernel, wide + extension, events, epilogue
@@ -421,6 +425,7 @@ void t4_destroy(t4_ctx *c) {
   if (c->candPool) (void)hipHostFree(c->candPool);
   if (c->aqRecDev) (void)hipFree(c->aqRecDev);
   if (c->aqRecRead) (void)hipFree(c->aqRecRead);
+  if (c->aqExtAux) (void)hipFree(c->aqExtAux);
   if (c->wideInit) {
     void *wp[] = {c->wide.seed, c->wide.bounds, c->wide.pCnt, c->wide.pRead, c->wide.pKeys, c->wide.gSize, c->wide.gInfo, c->wide.gCount, c->wide.gOff, c->wide.pRec,
                   c->wide.pRecCnt, c->wide.uniqPref, c->wide.mKeys, c->wide.mOrd, c->wide.sortTmp};
@@ -975,8 +980,9 @@ void launchTier(int grid, hipStream_t st, const T4IndexView &iv, const T4BatchVi
   else hipLaunchKernelGGL((t4k::queryKernel<CAP, MAXOV, NT, 0>), dim3(grid), dim3(NT), 0, st, iv, bv, wk, qa);
 }
 
-// Shared driver of t4_overlaps / t4_annotate_rough.
-int runQuery(t4_index *ix, t4_batch *b, T4QueryArgs qa, bool useBarcode, bool noHits = false) {
+// Shared driver of t4_overlaps / t4_annotate_rough. statusOut (nullable): the per-read status words are handed back instead of turned
+// into a refusal -- the rows of the reads with status 0 are final, the caller answers the others another way (t4_assign_wide).
+int runQuery(t4_index *ix, t4_batch *b, T4QueryArgs qa, bool useBarcode, bool noHits = false, std::vector<int> *statusOut = nullptr) {
   t4_ctx *c = ix->ctx;
   if (!ix->committed) return fail(c, T4_ERR_STATE, "index not committed");
   if (b->ctx != c) return fail(c, T4_ERR_ARG, "batch belongs to another ctx");
@@ -1049,6 +1055,7 @@ int runQuery(t4_index *ix, t4_batch *b, T4QueryArgs qa, bool useBarcode, bool no
   HIPCHK(c, hipEventElapsedTime(&msAll, c->ev[0], c->ev[2]));
   HIPCHK(c, hipEventElapsedTime(&msChain, c->ev[1], c->ev[2]));
   c->stats.kernel_ms = msAll; c->stats.chain_kernel_ms = msChain; c->stats.total_hits = (int64_t)hits;
+  if (statusOut) { statusOut->swap(status); return T4_OK; }
   for (long long i = 0; i < n; ++i)
     if (status[i] != 0)
       return fail(c, T4_ERR_UNSUPPORTED, "read %lld exceeds the engine limits (status %d: %s)", i, status[i],
@@ -1553,6 +1560,61 @@ int t4_assign_strands(t4_index *ix, t4_batch *b, const int32_t *strands, int32_t
   return T4_OK;
 }
 
+}  // extern "C"
+
+namespace {
+int assignWidePass2(t4_index *ix, t4_batch *b, const std::vector<int64_t> &todo, int strand, const int32_t *strands, int32_t *ret, t4_overlap *out);
+const int ASSIGN_WIDE_BATCH = 256;   // reads of one AddRead query call of pass 2 (its first launch gives every read a workgroup with a slice of global scratch)
+}  // namespace
+
+extern "C" {
+
+int t4_assign_wide(t4_index *ix, t4_batch *b, int strand, const int32_t *strands, int32_t *ret, t4_overlap *out) {
+  if (!ix || !b) return T4_ERR_ARG;
+  t4_ctx *c = ix->ctx;
+  c->assignWide[0] = c->assignWide[1] = 0;
+  if (ix->committed && ix->view.firstIsRef) return fail(c, T4_ERR_UNSUPPORTED, "t4_assign_wide needs a contig set (ExtendOverlap aligns against posWeight)");
+  if (!ix->committed) return fail(c, T4_ERR_STATE, "index not committed");
+  if (b->ctx != c) return fail(c, T4_ERR_ARG, "batch belongs to another ctx");
+  if (c->aq.active) return fail(c, T4_ERR_STATE, "an AddRead query is already in flight on this ctx");
+  if (b->n == 0) return T4_OK;
+  (void)hipSetDevice(c->device);
+  const size_t n = (size_t)b->n;
+  std::vector<int64_t> todo;   // the reads of pass 2
+  if (getenv("T4_ASSIGN_WIDE_ALL")) {   // testing aid, read once per call: every read takes the wide route (and none the tiers)
+    todo.resize(n);
+    for (size_t i = 0; i < n; ++i) todo[i] = (int64_t)i;
+  } else {
+    // pass 1: t4_assign / t4_assign_strands, with the reads beyond the tiers' limits reported instead of refused
+    int r;
+    if ((r = ensurePerCall(c, b->n))) return r;
+    if ((r = ensureResult(c, n))) return r;
+    DevBuf<int> dSt;
+    if (strands) {
+      if ((r = dSt.alloc(c, n))) return r;
+      HIPCHK(c, hipMemcpy(dSt, strands, sizeof(int) * n, hipMemcpyHostToDevice));
+    }
+    T4QueryArgs qa;
+    memset(&qa, 0, sizeof qa);
+    qa.mode = 2; qa.strand = strands ? 0 : strand; qa.strandPerRead = strands ? (const int *)dSt : nullptr; qa.skipRepeats = 0; qa.maxPerRead = 1;
+    qa.counts = nullptr; qa.out = c->result; qa.ret = c->counts;
+    std::vector<int> status;
+    if ((r = runQuery(ix, b, qa, true, false, &status))) return r;
+    if (ret) HIPCHK(c, hipMemcpy(ret, c->counts, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (out) HIPCHK(c, hipMemcpy(out, c->result, sizeof(t4_overlap) * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) if (status[i] != 0) todo.push_back((int64_t)i);
+  }
+  c->assignWide[0] = (int64_t)(n - todo.size()); c->assignWide[1] = (int64_t)todo.size();
+  if (todo.empty()) return T4_OK;
+  return assignWidePass2(ix, b, todo, strand, strands, ret, out);
+}
+
+int t4_assign_wide_stats(t4_ctx *c, int64_t *out2) {
+  if (!c || !out2) return T4_ERR_ARG;
+  out2[0] = c->assignWide[0]; out2[1] = c->assignWide[1];
+  return T4_OK;
+}
+
 int t4_posweight_recompute(t4_index *ix, t4_batch *b, const t4_overlap *assign, const int32_t *mult, int32_t *posweight, int64_t posweight_cap) {
   return t4_consensus_recompute(ix, b, assign, mult, posweight, posweight_cap, nullptr, 0, nullptr);
 }
@@ -1670,6 +1732,7 @@ int aqLaunch(t4_ctx *c);
 int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const int32_t *viewOf, bool smallFirst, int n, const char *bases,
             const int64_t *offsets, const int32_t *barcodes, const int32_t *strands, int skip_repeats, const double *factors,
             unsigned char *tierHint = nullptr, bool lean = false, const int32_t *onlySeq = nullptr, const int32_t *forceMin = nullptr, int wantCands = 0) {
+  // (wantCands: bit 0 the candidate store, bit 1 T4CandArgs::extAux)
   (void)hipSetDevice(c->device);
   AqCall &q = c->aq;
   if (q.active) return fail(c, T4_ERR_STATE, "an AddRead query is already in flight on this ctx");
@@ -1691,7 +1754,7 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   q.oVw = al8(q.oLs + sizeof(int) * (size_t)n); q.oFa = al8(q.oVw + sizeof(int) * (size_t)n); q.oOnly = al8(q.oFa + sizeof(double) * (size_t)n);
   q.oForce = al8(q.oOnly + sizeof(int) * (size_t)n);
   q.oCs = al8(q.oForce + sizeof(int) * (size_t)n);
-  q.oWide = al8(q.oCs + sizeof(T4CandArgs)); q.hasOnly = onlySeq != nullptr; q.hasForce = forceMin != nullptr; q.wantCands = (wantCands & 1) != 0;
+  q.oWide = al8(q.oCs + sizeof(T4CandArgs)); q.hasOnly = onlySeq != nullptr; q.hasForce = forceMin != nullptr; q.wantCands = (wantCands & 1) != 0; q.keepExtAux = (wantCands & 2) != 0;
   q.oWideA = al8(q.oWide + sizeof(T4Wide)); q.inBytes = al8(q.oWideA + sizeof(T4Wide));
   q.pCnt = 0; q.pSta = al8(q.pCnt + sizeof(int) * (size_t)n); q.pNext = al8(q.pSta + sizeof(int) * (size_t)n);
   q.pNext2 = al8(q.pNext + sizeof(int) * (size_t)n); q.pBase = al8(q.pNext2 + sizeof(int) * (size_t)n);
@@ -1842,6 +1905,14 @@ int aqLaunch(t4_ctx *c) {
     memset(&cs, 0, sizeof cs);
     cs.stats8 = (int *)(c->aqOut + q.pS8);
     if (q.hasForce) cs.forceMin = (const int *)(c->aqIn + q.oForce);
+    if (q.keepExtAux) {   // (sized with the pool: a call repeated with a larger pool comes through here again)
+      if (c->aqExtAuxCap < c->aqPoolCap) {
+        c->aqExtAuxCap = 0;
+        if ((r = devAlloc(c, &c->aqExtAux, (size_t)c->aqPoolCap))) return r;
+        c->aqExtAuxCap = c->aqPoolCap;
+      }
+      cs.extAux = c->aqExtAux;
+    }
     if (q.wantCands) {
       cs.candOut = c->candPoolDev; cs.candCap = c->candCap; cs.candCursor = (unsigned *)(c->aqOut + q.pTail + 32); cs.candOverflow = (int *)(c->aqOut + q.pTail + 36);
       cs.candBase = (int *)(c->aqOut + q.pCb); cs.candCnt = (int *)(c->aqOut + q.pCc);
@@ -2200,6 +2271,61 @@ int addQueryImpl(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, c
   }
   return T4_OK;
 }
+
+// Pass 2 of t4_assign_wide: the reads `todo` of the batch through the AddRead query path (GetOverlapsFromRead(read, strand, barcode,
+// 0, false) and the ExtendOverlap of every overlap, factor 1.0 / 2.0 by barcode -- what AssignRead runs), which has the wide query
+// behind it, and AssignRead's pick over the records of every read on the device (assignPickKernel). The batch holds the reads
+// packed; the query path takes characters, so the packed words come back once.
+int assignWidePass2(t4_index *ix, t4_batch *b, const std::vector<int64_t> &todo, int strand, const int32_t *strands, int32_t *ret, t4_overlap *out) {
+  t4_ctx *c = ix->ctx;
+  const size_t n = (size_t)b->n, wpk = (size_t)b->wpk, wnm = (size_t)b->wnm;
+  std::vector<unsigned> pk(n * wpk), nm(n * wnm);
+  std::vector<int> len(n), bc;
+  HIPCHK(c, hipMemcpy(pk.data(), b->dPk, sizeof(unsigned) * pk.size(), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(nm.data(), b->dNm, sizeof(unsigned) * nm.size(), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(len.data(), b->dLen, sizeof(int) * n, hipMemcpyDeviceToHost));
+  if (b->dBarcode) { bc.resize(n); HIPCHK(c, hipMemcpy(bc.data(), b->dBarcode, sizeof(int) * n, hipMemcpyDeviceToHost)); }
+  DevBuf<int> dRet;
+  DevBuf<T4OverlapOut> dOut;
+  int r;
+  if ((r = dRet.alloc(c, ASSIGN_WIDE_BATCH)) || (r = dOut.alloc(c, ASSIGN_WIDE_BATCH))) return r;
+  std::string bases;
+  std::vector<int64_t> off;
+  std::vector<int32_t> bcs, sts, hRet(ASSIGN_WIDE_BATCH);
+  std::vector<double> factors;
+  std::vector<t4_overlap> hOut(ASSIGN_WIDE_BATCH);
+  for (size_t at = 0; at < todo.size(); at += ASSIGN_WIDE_BATCH) {
+    const int m = (int)(todo.size() - at < (size_t)ASSIGN_WIDE_BATCH ? todo.size() - at : (size_t)ASSIGN_WIDE_BATCH);
+    bases.clear(); off.assign(1, 0); bcs.clear(); sts.clear(); factors.clear();
+    for (int j = 0; j < m; ++j) {
+      const size_t i = (size_t)todo[at + j];
+      const unsigned *p = pk.data() + i * wpk, *q = nm.data() + i * wnm;
+      for (int x = 0; x < len[i]; ++x) bases.push_back(((q[x >> 5] >> (x & 31)) & 1u) ? 'N' : "ACGT"[(p[x >> 4] >> ((x & 15) * 2)) & 3u]);
+      off.push_back((int64_t)bases.size());
+      const int barcode = bc.empty() ? -1 : bc[i];
+      bcs.push_back(barcode); sts.push_back(strands ? strands[i] : strand); factors.push_back(barcode == -1 ? 1.0 : 2.0);
+    }
+    if ((r = aqBegin(c, ix->view, nullptr, nullptr, false, m, bases.c_str(), off.data(), bc.empty() ? nullptr : bcs.data(), sts.data(), 0, factors.data(),
+                     nullptr, false, nullptr, nullptr, 2))) return r;
+    AqResult res;
+    if ((r = aqEnd(c, &res))) return r;
+    const AqCall &q = c->aq;
+    const size_t rec = (size_t)c->aqPoolCap;
+    const T4OverlapOut *ov = (const T4OverlapOut *)c->aqPoolDev;
+    launch(t4k::assignPickKernel, m, T4_PICK_THREADS, c->stream, m, (const int *)(c->aqOut + q.pCnt), (const int *)(c->aqOut + q.pBase),
+           (const int *)(c->aqIn + q.oLen), ov, ov + rec, (const int *)(ov + 2 * rec), c->aqExtAux, c->aqPoolCap, dRet, dOut);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hRet.data(), dRet, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hOut.data(), dOut, sizeof(t4_overlap) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ++c->syncEpoch;
+    for (int j = 0; j < m; ++j) {
+      if (ret) ret[todo[at + j]] = hRet[j];
+      if (out) out[todo[at + j]] = hOut[j];
+    }
+  }
+  return T4_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2284,6 +2410,34 @@ int t4_add_query_last_stable(t4_ctx *c, const int32_t **flags, int *n) {
   if (!c || !flags) return T4_ERR_ARG;
   *flags = c->aqLastStable;
   if (n) *n = c->aqLastN;
+  return T4_OK;
+}
+
+int t4_assign_pick(t4_ctx *c, int n_reads, const int32_t *counts, const int32_t *base, const int32_t *lens, int64_t n_rec, const t4_overlap *ov,
+                   const t4_overlap *ext, const int32_t *ret, const int32_t *aux, int32_t *out_ret, t4_overlap *out) {
+  if (!c || n_reads < 0 || n_rec < 0 || n_rec > 0x7FFFFFFF || (n_reads > 0 && (!counts || !base || !lens || !out_ret || !out)) || (n_rec > 0 && (!ov || !ext || !ret || !aux))) return T4_ERR_ARG;
+  if (n_reads == 0) return T4_OK;
+  (void)hipSetDevice(c->device);
+  const size_t n = (size_t)n_reads, m = (size_t)n_rec;
+  DevBuf<int> dCnt, dBase, dLen, dRet, dAux, dOutRet;
+  DevBuf<T4OverlapOut> dOv, dExt, dOut;
+  int r;
+  if ((r = dCnt.alloc(c, n)) || (r = dBase.alloc(c, n)) || (r = dLen.alloc(c, n)) || (r = dOutRet.alloc(c, n)) || (r = dOut.alloc(c, n)) ||
+      (r = dOv.alloc(c, m)) || (r = dExt.alloc(c, m)) || (r = dRet.alloc(c, m)) || (r = dAux.alloc(c, m))) return r;
+  HIPCHK(c, hipMemcpy(dCnt, counts, sizeof(int) * n, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dBase, base, sizeof(int) * n, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dLen, lens, sizeof(int) * n, hipMemcpyHostToDevice));
+  if (m) {
+    HIPCHK(c, hipMemcpy(dOv, ov, sizeof(t4_overlap) * m, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dExt, ext, sizeof(t4_overlap) * m, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dRet, ret, sizeof(int) * m, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dAux, aux, sizeof(int) * m, hipMemcpyHostToDevice));
+  }
+  launch(t4k::assignPickKernel, n_reads, T4_PICK_THREADS, c->stream, n_reads, dCnt, dBase, dLen, dOv, dExt, dRet, dAux, (int)n_rec, dOutRet, dOut);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out_ret, dOutRet, sizeof(int) * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out, dOut, sizeof(t4_overlap) * n, hipMemcpyDeviceToHost));
   return T4_OK;
 }
 

@@ -181,6 +181,8 @@ struct T4CandArgs {
   int *candBase, *candCnt;   // null with candOut
   int *stats8;
   const int *forceMin;       // nullable
+  int *extAux;               // nullable, one word per pool record: what ExtendOverlap's own record holds and the public one cannot carry -- 0 when the
+                             // extension failed the similarity cut, else the denominator of its similarity (assignPickKernel reads it)
 };
 // Bits 5-6 of a contig's predicate byte at offset o: the number of postings (contig, o) the index holds (0-3); bit 7 of the byte at
 // offset 0: the marks of this contig are not to be trusted (an offset with more than three postings). Written by the ordered

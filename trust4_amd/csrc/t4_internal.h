@@ -99,5 +99,12 @@ int t4_add_query_groups(t4_ctx *ctx, int i, const t4_grp **groups, int *n, int *
 int t4_add_query_wide_stats(t4_ctx *ctx, int64_t *out4);
 int t4_add_query_defer_stats(t4_ctx *ctx, int64_t *out1);
 int t4_add_query_last_call(t4_ctx *ctx, double *kernel_ms, const int32_t **ticks10ns, int *n);   // development aid (T4_ROUND_LOG)
+// AssignRead's pick over caller-supplied records (assignPickKernel as t4_assign_wide runs it, one workgroup per read): counts[i] records of
+// read i (lens[i] bases) start at base[i] of ov (GetOverlapsFromRead's), ext / ret (ExtendOverlap's result and return value) and aux
+// (0: the extension failed the similarity cut, else the denominator of its similarity), n_rec records each. For the tests of the
+// pick: contig sets leave indelCnt 0 in every overlap GetOverlapsFromRead returns, so the field AssignRead leaves behind after a
+// similarity-failed extension is only seen to move with records made by hand.
+int t4_assign_pick(t4_ctx *ctx, int n_reads, const int32_t *counts, const int32_t *base, const int32_t *lens, int64_t n_rec, const t4_overlap *ov,
+                   const t4_overlap *ext, const int32_t *ret, const int32_t *aux, int32_t *out_ret, t4_overlap *out);
 
 }  // extern "C"

@@ -3669,6 +3669,7 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
     PHASE_MARK(ws, 16);
     extendOverlaps(ix, wm, ws, n, len, false, qa.factorPerRead[r], sides, dirbuf, wm.dirBytes, res, qa.leanExt != 0);
     PHASE_MARK(ws, 17);
+    int *const extAux = qa.cs ? qa.cs->extAux : nullptr;
     for (int i = lane; i < n; i += NT) {
       const OvRec &o = wm.fin[i];
       T4OverlapOut t;
@@ -3678,6 +3679,7 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
       else { t.indelCnt = 0; t.similarity = (double)t.matchCnt / (double)res[i].den; }
       qa.outExt[base + i] = t;
       qa.ret[base + i] = res[i].ret;
+      if (extAux) extAux[base + i] = res[i].simFail ? 0 : res[i].den;
     }
     if (lane == 0) qa.counts[r] = ret;
   } else if (VARIANT == 1 && (qa.mode == 2 || qa.mode == 3)) {
@@ -4100,10 +4102,112 @@ __global__ __launch_bounds__(64) void extendKernel(T4IndexView ix, T4BatchView b
         else { t.indelCnt = 0; t.similarity = (double)t.matchCnt / (double)e.den; }
         qa.outExt[i0 + lane] = t;
         qa.ret[i0 + lane] = e.ret;
+        if (qa.cs && qa.cs->extAux) qa.cs->extAux[i0 + lane] = e.simFail ? 0 : e.den;
       }
       if (lane == 0 && s_ws.unsupported) qa.poolCursor[1] = 1u;   // an overhang beyond the direction buffer (reads of more than 600 bases)
       __syncthreads();
       i0 = i1;
+    }
+  }
+}
+
+// The pick of SeqSet::AssignRead (SeqSet.hpp:4649-4699) over the records an AddRead query call left in its result pool, for reads
+// beyond the single-workgroup tiers (t4_assign_wide): AssignRead sorts the overlaps by operator< with the scored similarity, extends
+// them in that order and stops at the first extension that returned 1 and spans the read. Nothing else of the sorted order is
+// observable, so the sort becomes two reductions under ovCmp(., ., true), ties to the lower pool index (the `cm == 0 && j < i` of
+// mode 2's rank sort):
+//   hit        = the minimum over the records with ret == 1 && readStart == 0 && readEnd == len - 1
+//   staleIndel = indelCnt of the maximum among the records before `hit` whose extension failed the similarity cut (0 without one):
+//                `extendedOverlap = overlap` of SeqSet.hpp:1243-1246 leaves that field behind and the later calls do not reset it
+// One workgroup per read, a strided loop with every lane's running best in registers (a read may have 2^20 records: no rank sort),
+// then a wave reduction and an LDS reduction across the waves. extAux: T4CandArgs::extAux of the call that filled the pool.
+struct PickBest { int idx, seqIdx, rs, re, ss, se, matchCnt, flags; };   // idx < 0: none
+__device__ __forceinline__ OvRec pickRec(const PickBest &b) {
+  OvRec o;
+  o.seqIdx = b.seqIdx; o.rs = b.rs; o.re = b.re; o.ss = b.ss; o.se = b.se; o.matchCnt = b.matchCnt; o.indelCnt = 0; o.chainPos = 0; o.chainLen = 0; o.flags = b.flags;
+  return o;
+}
+__device__ __forceinline__ PickBest pickLoad(const T4OverlapOut *ov, int i) {
+  const T4OverlapOut t = ov[i];
+  PickBest b;
+  b.idx = i; b.seqIdx = t.seqIdx; b.rs = t.readStart; b.re = t.readEnd; b.ss = t.seqStart; b.se = t.seqEnd; b.matchCnt = t.matchCnt;
+  b.flags = (t.strand == 1 ? OV_PLUS : 0) | (t.similarity == 0 ? OV_SIMZERO : 0);
+  return b;
+}
+// does a stand before b in AssignRead's sorted order?
+__device__ __forceinline__ bool pickBefore(const PickBest &a, const PickBest &b) {
+  const int cm = ovCmp(pickRec(a), pickRec(b), true);
+  return cm < 0 || (cm == 0 && a.idx < b.idx);
+}
+__device__ __forceinline__ PickBest pickShflXor(const PickBest &b, int d) {
+  PickBest o;
+  o.idx = __shfl_xor(b.idx, d); o.seqIdx = __shfl_xor(b.seqIdx, d); o.rs = __shfl_xor(b.rs, d); o.re = __shfl_xor(b.re, d);
+  o.ss = __shfl_xor(b.ss, d); o.se = __shfl_xor(b.se, d); o.matchCnt = __shfl_xor(b.matchCnt, d); o.flags = __shfl_xor(b.flags, d);
+  return o;
+}
+// the first (wantLast: the last) in sorted order of every lane's candidate, in every lane; `red` holds one record per wave. Two barriers.
+__device__ __forceinline__ PickBest pickReduce(PickBest b, bool wantLast, PickBest *red) {
+  for (int d = 32; d > 0; d >>= 1) {
+    const PickBest o = pickShflXor(b, d);
+    if (o.idx >= 0 && (b.idx < 0 || pickBefore(o, b) != wantLast)) b = o;
+  }
+  const int wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  if (laneId() == 0) red[wave] = b;
+  __syncthreads();
+  b = red[0];
+  for (int w = 1; w < nw; ++w) {
+    const PickBest o = red[w];
+    if (o.idx >= 0 && (b.idx < 0 || pickBefore(o, b) != wantLast)) b = o;
+  }
+  __syncthreads();
+  return b;
+}
+#define T4_PICK_THREADS 256
+// counts / outBase / lens: the per-read arrays of the query call; ov / ext / ret / extAux its pool of poolCap records. outRet[r] / out[r]
+// receive what mode 2 of the query kernel writes for a read.
+__global__ __launch_bounds__(T4_PICK_THREADS) void assignPickKernel(int nReads, const int *counts, const int *outBase, const int *lens,
+                                                                    const T4OverlapOut *ov, const T4OverlapOut *ext, const int *ret, const int *extAux,
+                                                                    int poolCap, int *outRet, T4OverlapOut *out) {
+  __shared__ PickBest s_red[T4_PICK_THREADS / 64];
+  const int lane = tid(), NT = nthr();
+  for (int r = blockIdx.x; r < nReads; r += gridDim.x) {
+    const int len = lens[r];
+    int n = counts[r], base = n > 0 ? outBase[r] : 0;
+    if (n < 0 || base < 0 || base > poolCap) n = 0;
+    if (n > poolCap - base) n = poolCap - base;
+    PickBest best;
+    best.idx = -1; best.seqIdx = 0; best.rs = best.re = best.ss = best.se = 0; best.matchCnt = 0; best.flags = 0;
+    PickBest none = best;
+    for (int i = base + lane; i < base + n; i += NT) {
+      if (ret[i] != 1) continue;
+      const T4OverlapOut e = ext[i];
+      if (e.readStart != 0 || e.readEnd != len - 1) continue;
+      const PickBest me = pickLoad(ov, i);
+      if (best.idx < 0 || pickBefore(me, best)) best = me;
+    }
+    const PickBest hit = pickReduce(best, false, s_red);
+    PickBest stale = none;
+    if (hit.idx >= 0) {
+      for (int i = base + lane; i < base + n; i += NT) {
+        if (extAux[i] != 0 || i == hit.idx) continue;   // (the hit itself returned 1: it did not fail the cut)
+        const PickBest me = pickLoad(ov, i);
+        if (pickBefore(me, hit) && (stale.idx < 0 || pickBefore(stale, me))) stale = me;
+      }
+    }
+    stale = pickReduce(stale, true, s_red);
+    if (lane == 0) {
+      T4OverlapOut t;
+      if (hit.idx >= 0) {
+        const T4OverlapOut e = ext[hit.idx];
+        t.seqIdx = hit.seqIdx; t.readStart = e.readStart; t.readEnd = e.readEnd; t.seqStart = e.seqStart; t.seqEnd = e.seqEnd;
+        t.strand = (hit.flags & OV_PLUS) ? 1 : -1; t.matchCnt = e.matchCnt; t.indelCnt = stale.idx >= 0 ? ov[stale.idx].indelCnt : 0;
+        t.similarity = (double)e.matchCnt / (double)extAux[hit.idx];
+        outRet[r] = hit.seqIdx;
+      } else {
+        t.seqIdx = -1; t.readStart = t.readEnd = t.seqStart = t.seqEnd = -1; t.strand = 1; t.matchCnt = 0; t.indelCnt = 0; t.similarity = 0;
+        outRet[r] = -1;
+      }
+      out[r] = t;
     }
   }
 }
