@@ -171,8 +171,11 @@ int t4_assign_strands(t4_index *ix, t4_batch *b, const int32_t *strands, int32_t
  * 262 144 hits, more than 16 384 overlaps) is answered like the reference: GetOverlapsFromRead(read, strand, barcode, 0, false) and
  * the ExtendOverlap of every overlap (factor 1.0, with a barcode 2.0) run on the path of t4_add_query, which has the wide query
  * behind it, and AssignRead's pick over its records runs on the device. A read that path refuses too keeps the refusal, with that
- * path's message (the hits of one contig overflowing a partition, an overhang beyond the direction buffer; a read WITH a barcode
- * stays off the wide query, so one that meets more than 10 000 postings in one (k-mer, barcode) list is still refused). Fails with
+ * path's message (the hits of one contig overflowing a partition, an overhang beyond the direction buffer). A read WITH a barcode
+ * on an index that is not keyed by barcode is answered too: a posting of a contig with another barcode is no hit and every hit
+ * counts repeats = 1, so a list beyond 10 000 postings changes nothing for it (SeqSet.hpp:1406-1418). On an index that IS keyed by
+ * barcode (consider_barcode = 1) a barcoded read stays off the wide query, and one that meets more than 10 000 postings in one
+ * (k-mer, barcode) list is still refused. Fails with
  * T4_ERR_STATE while an AddRead query is in flight on the ctx (t4_assembler's windows use the same pools). Contig sets only.
  * T4_ASSIGN_WIDE_ALL (environment, testing aid, read once per call): every read takes the second path; no result changes.
  * t4_assign_wide_stats: of the last call on the ctx, out2[0] = reads the tiers answered, out2[1] = reads answered the other way. */
@@ -225,7 +228,14 @@ int t4_gap_dp_align(t4_ctx *ctx, int kind, int impl, int n, const int64_t *t_off
 /* The query half of SeqSet::AddRead for a (small) batch of reads in ONE launch and one host round trip:
  * GetOverlapsFromRead(read, strands[i], barcode, 0, skip_repeats) (SeqSet.hpp:3437) and the ExtendOverlap
  * (SeqSet.hpp:3597 / 3746, mismatch factor factors[i]) of every overlap it returns. Layout as t4_overlaps /
- * t4_extend. Used by t4_assembler for its speculation windows. Contig sets only. */
+ * t4_extend. Used by t4_assembler for its speculation windows. Contig sets only.
+ * Reach: a read that outgrows one workgroup (more than T4_WIDE_MIN_HITS emitted hits, a posting list beyond 10 000 entries, more
+ * overlaps than the tier holds) is served by the wide query, one read over the whole chip -- also either pass of a skip_repeats
+ * query (--trimLevel 2: the first pass drops every list of 100 or more postings and runs with filter 0; the plain pass follows only
+ * when the first finds no overlap, as a second sweep of the wide kernels) and a read with a barcode on an index that is not keyed
+ * by barcode. Still refused (T4_ERR_UNSUPPORTED): a barcoded read beyond the single-workgroup limits on an index keyed by barcode
+ * (consider_barcode = 1), the hits of ONE contig with one read beyond a partition (8 192), an overhang alignment beyond the
+ * extension kernel's direction buffer. */
 int t4_add_query(t4_index *ix, int n, const char *bases, const int64_t *offsets, const int32_t *barcodes,
                  const int32_t *strands, int skip_repeats, const double *factors, int max_per_read, int32_t *counts,
                  t4_overlap *ov, t4_overlap *ext, int32_t *ext_ret);
@@ -286,12 +296,13 @@ int t4_assembler_prefetch(t4_assembler *a, int n, const char *const *reads, cons
 int t4_assembler_window_valid(const t4_assembler *a);
 /* Host threads that derive the window's dependency sets while the GPU runs a query batch (default 1). */
 int t4_assembler_set_threads(t4_assembler *a, int host_threads);
-/* Counters of a set whose index is not keyed by barcode (device image by deltas, sliding window), up to 23 values:
+/* Counters of a set whose index is not keyed by barcode (device image by deltas, sliding window), up to 28 values:
  * query rounds, reads queried, deltas, delta bytes, invalidations (total; by an index change of one of the read's keys; by a
  * list crossing 100 postings; by a changed region within reach; by a left extension; by a whole-contig change; by exhausted
  * tolerance), tolerated index changes, microseconds in deltas / dependency sets / event examination / query batches; then of
  * the ctx's AddRead query path: calls, reads, launches of the global-scratch tier, reads it served, result records,
- * microseconds of its kernels (HIP events), _hit records its seed stages emitted. */
+ * microseconds of its kernels (HIP events), _hit records its seed stages emitted; [23..26] of its wide query: reads served,
+ * partitions, calls repeated with larger pools, dependency records; [27] window entries the wide query served (all lanes). */
 int t4_assembler_live_counters(const t4_assembler *a, int64_t *out, int n);
 /* The chain of dependent query rounds of a live set ("the floor"): up to 10 values -- rounds; rounds that carried restricted
  * re-queries only; 5th percentile and median of a round's kernel milliseconds (HIP events); 5th percentile and median of a round's

@@ -75,6 +75,8 @@ struct AqCall {
   bool hasOnly = false, hasForce = false, wantCands = false;
   bool keepExtAux = false;   // t4_assign_wide: one word per pool record beside the public records (T4CandArgs::extAux)
   bool extendLater = false, wide = false, onlyRestricted = false;
+  bool sweep2Done = false;     // the second sweep of the wide kernels (first passes of skipRepeats queries that found nothing) has been looked at
+  int nWideSlots = 0;          // read slots per half of the wide query's header arrays (2 n for a skipRepeats call: a read may take one per sweep)
   bool lazyDone = false, lazyStage = false;   // the wide pipeline behind the query kernel is launched only once the kernel is known to have deferred a read (aqEnd)
   int wideSafety = 32;   // of sixteenths: partitions are planned for half of their capacity
   T4BatchView bv; T4QueryArgs qa; T4Work wk;
@@ -316,6 +318,7 @@ int ensureWide(t4_ctx *c, int reads, int parts, int groups) {
     if ((r = devAlloc(c, &w.bounds, 2 * (size_t)n * (T4_WIDE_MAXP + 1)))) return r;
     if ((r = devAlloc(c, &w.uniqPref, 2 * (size_t)n * (w.pcap + 1)))) return r;
     if ((r = devAlloc(c, &w.sortTmp, 2 * (size_t)n * 2 * w.pcap))) return r;
+    if ((r = devAlloc(c, &w.requeue, 2 * (size_t)n))) return r;
     w.maxReads = n;
   }
   if (parts > w.maxPart) {
@@ -353,7 +356,7 @@ T4Wide wideHalf(const t4_ctx *c, int half) {
   T4Wide w = c->wide;
   if (!half) return w;
   const size_t R = (size_t)w.maxReads, P = (size_t)w.maxPart;
-  w.seed += R * T4_WIDE_SEEDS; w.bounds += R * (T4_WIDE_MAXP + 1); w.uniqPref += R * (w.pcap + 1); w.sortTmp += R * 2 * w.pcap;
+  w.seed += R * T4_WIDE_SEEDS; w.bounds += R * (T4_WIDE_MAXP + 1); w.uniqPref += R * (w.pcap + 1); w.sortTmp += R * 2 * w.pcap; w.requeue += R;
   w.pCnt += P; w.pRead += P; w.pKeys += P * w.pcap; w.gSize += P * w.pcap; w.gInfo += P * w.pcap; w.gCount += P * 4; w.gOff += P * 2;
   w.pRec += P * w.maxOvPart * 10; w.pRecCnt += P; w.mKeys += P * w.maxOvPart; w.mOrd += P * w.maxOvPart;
   w.grpPool += w.grpCap;
@@ -428,7 +431,7 @@ void t4_destroy(t4_ctx *c) {
   if (c->aqExtAux) (void)hipFree(c->aqExtAux);
   if (c->wideInit) {
     void *wp[] = {c->wide.seed, c->wide.bounds, c->wide.pCnt, c->wide.pRead, c->wide.pKeys, c->wide.gSize, c->wide.gInfo, c->wide.gCount, c->wide.gOff, c->wide.pRec,
-                  c->wide.pRecCnt, c->wide.uniqPref, c->wide.mKeys, c->wide.mOrd, c->wide.sortTmp};
+                  c->wide.pRecCnt, c->wide.uniqPref, c->wide.mKeys, c->wide.mOrd, c->wide.sortTmp, c->wide.requeue};
     for (void *p : wp) if (p) (void)hipFree(p);
     if (c->grpPoolHost) (void)hipHostFree(c->grpPoolHost);
   }
@@ -1761,9 +1764,11 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   q.pTick = al8(q.pBase + sizeof(int) * (size_t)n); q.pStab = al8(q.pTick + sizeof(int) * (size_t)n); q.pAux = al8(q.pStab + sizeof(int) * (size_t)n);
   q.pN4 = al8(q.pAux + sizeof(int) * (size_t)n); q.pCb = al8(q.pN4 + sizeof(int) * (size_t)n); q.pCc = al8(q.pCb + sizeof(int) * (size_t)n);
   q.pS8 = al8(q.pCc + sizeof(int) * (size_t)n); q.pTail = al8(q.pS8 + sizeof(int) * T4_QSTATS * (size_t)n);   // tail: overflow1 | overflow2 | hits (8 B) | pool cursor | dir overflow | cand cursor | cand overflow | reads deferred to extendKernel
-  q.pWctl = q.pTail + 48; q.pWplan = q.pWctl + 32; q.pWstat = al8(q.pWplan + sizeof(T4WidePlan) * (size_t)n);
-  q.pWctlA = al8(q.pWstat + sizeof(int) * T4_WIDE_STAT * (size_t)n); q.pWplanA = q.pWctlA + 32; q.pWstatA = al8(q.pWplanA + sizeof(T4WidePlan) * (size_t)n);
-  q.outBytes = al8(q.pWstatA + sizeof(int) * T4_WIDE_STAT * (size_t)n);
+  const size_t nW = (size_t)n * (skip_repeats ? 2 : 1);   // (a first pass that finds nothing leaves its slot and takes a new one in the second sweep)
+  q.nWideSlots = (int)nW;
+  q.pWctl = q.pTail + 48; q.pWplan = q.pWctl + 32; q.pWstat = al8(q.pWplan + sizeof(T4WidePlan) * nW);
+  q.pWctlA = al8(q.pWstat + sizeof(int) * T4_WIDE_STAT * nW); q.pWplanA = q.pWctlA + 32; q.pWstatA = al8(q.pWplanA + sizeof(T4WidePlan) * nW);
+  q.outBytes = al8(q.pWstatA + sizeof(int) * T4_WIDE_STAT * nW);
   q.wideSafety = c->wideSafetyKeep;
   if (q.inBytes > c->aqInBytes) {
     if (c->aqIn) (void)hipFree(c->aqIn);
@@ -1809,7 +1814,8 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   }
   // one big contig set, plain passes: a read beyond the LDS tier goes to the wide query (t4_wide.h) instead of one workgroup's
   // global scratch -- decided on the device, inside the one launch every read starts in (T4_WIDE_OFF: the global-scratch tier as before)
-  q.wide = !views && !smallFirst && !skip_repeats && base.hasNovel == 2 && !getenv("T4_WIDE_OFF");   // (read per call: tests/test_wide_query.py switches it between two calls on one ctx)   // (a read with a barcode stays on the old path: wideWant in processRead)
+  // (skipRepeats queries -- --trimLevel 2 -- and barcoded reads on an index that is not keyed by barcode are deferred too: wideWant in processRead)
+  q.wide = !views && !smallFirst && base.hasNovel == 2 && !getenv("T4_WIDE_OFF");   // (read per call: tests/test_wide_query.py switches it between two calls on one ctx)
   q.onlyRestricted = false;
   if (onlySeq) {   // a round of restricted re-queries only defers nothing: the wide query's five grids stay unlaunched, and its reads
     bool anyWhole = false;   // (a few overlaps with one contig each) extend inside the query kernel -- no extendKernel behind it
@@ -1820,7 +1826,8 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   const bool forceGlobal = c->aqEnv.forceGlobal;   // testing aid: every read on the global-scratch tier
   if (forceGlobal && !smallFirst) { q.allGlobal.assign((size_t)n, 1); q.tierHint = tierHint = q.allGlobal.data(); q.wide = false; }
   // (with the wide query on, a hinted read -- served wide the last time -- starts on the second stream: wideSeedKernel)
-  auto direct = [&](int i) { return tierHint && tierHint[i] && !smallFirst && !(onlySeq && onlySeq[i] >= 0); };
+  // (not a barcoded read on an index keyed by barcode: those stay with one workgroup)
+  auto direct = [&](int i) { return tierHint && tierHint[i] && !smallFirst && !(onlySeq && onlySeq[i] >= 0) && !(q.wide && base.considerBarcode && barcodes && barcodes[i] != -1); };
   int nFirst = 0, nDirect = 0;
   for (int i = 0; i < n; ++i) if (!direct(i)) ls[nFirst++] = i;
   for (int i = 0; i < n; ++i) if (direct(i)) ls[nFirst + nDirect++] = i;
@@ -1886,9 +1893,9 @@ int aqLaunch(t4_ctx *c) {
   auto tl_ = q.tf0;
   auto lapL = [&](int i) { const auto t = std::chrono::steady_clock::now(); c->aqSecLaunch[i] += std::chrono::duration<double>(t - tl_).count(); tl_ = t; };
   if (q.wide) {
-    if ((r = ensureWide(c, n, 1, 1))) return r;
+    if ((r = ensureWide(c, q.nWideSlots, 1, 1))) return r;
     T4Wide w = wideHalf(c, 0), wa = wideHalf(c, 1);
-    w.enabled = 1; w.safetyNum = q.wideSafety;
+    w.enabled = 1; w.safetyNum = q.wideSafety; w.firstRead = w.firstPart = 0;
     // Reads of up to T4_WIDE_MIN_HITS emitted hits stay with one workgroup (LDS tier, then its slice of global scratch inside the same
     // launch, beside the other reads of the round): the wide query's kernels run behind the launch and cost a round about 0.25 ms
     // whatever the read is (profiles/r04b-h); from the LDS tier.s capacity on it beats one workgroup.s global scratch (C2 122 -> 93 s, profiles/r04h_*). The testing aid T4_AQ_CAP_LIMIT lowers
@@ -1896,7 +1903,7 @@ int aqLaunch(t4_ctx *c) {
     { const int lim = c->aqEnv.capLimit; w.minHits = lim > 0 ? lim : c->aqEnv.wideMinHits; }
     w.ctl = (int *)(c->aqOut + q.pWctl); w.plan = (T4WidePlan *)(c->aqOut + q.pWplan); w.stat = (int *)(c->aqOut + q.pWstat);
     memcpy(c->aqInHost + q.oWide, &w, sizeof w);
-    wa.enabled = 1; wa.safetyNum = w.safetyNum; wa.minHits = w.minHits;
+    wa.enabled = 1; wa.safetyNum = w.safetyNum; wa.minHits = w.minHits; wa.firstRead = wa.firstPart = 0;
     wa.ctl = (int *)(c->aqOut + q.pWctlA); wa.plan = (T4WidePlan *)(c->aqOut + q.pWplanA); wa.stat = (int *)(c->aqOut + q.pWstatA);
     memcpy(c->aqInHost + q.oWideA, &wa, sizeof wa);
   }
@@ -2000,7 +2007,7 @@ int aqLaunch(t4_ctx *c) {
       const int cus = c->cus > 0 ? c->cus : 1;
       auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; };
       const int gParts = clampi(2 * c->wideRecentParts + 4 * nDirect + 4, 4, cus * 2), gReads = clampi(nDirect, 1, cus < 64 ? cus : 64);
-      hipLaunchKernelGGL(t4k::wideSeedKernel, dim3(nDirect < cus ? nDirect : cus), dim3(512), 0, c->stream2, q.base, bv, wd, qa, wa, wd.list, nDirect);
+      hipLaunchKernelGGL(t4k::wideSeedKernel, dim3(nDirect < cus ? nDirect : cus), dim3(512), 0, c->stream2, q.base, bv, wd, qa, wa, wd.list, nDirect, q.skipRepeats ? 1 : 0);
       hipLaunchKernelGGL(t4k::wideScatterKernel, dim3(clampi(8 * gParts, 16, cus * 8)), dim3(256), 0, c->stream2, q.base, wa);
       hipLaunchKernelGGL((t4k::wideSortKernel<8192>), dim3(gParts), dim3(512), 0, c->stream2, q.base, wa);
       hipLaunchKernelGGL(t4k::wideStatsKernel, dim3(gReads), dim3(512), 0, c->stream2, q.base, wa);
@@ -2030,7 +2037,7 @@ int aqLaunch(t4_ctx *c) {
   }
   lapL(3);
   if (nDirect > 0 && !q.wide) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evG, 0));
-  q.lazyDone = false; q.lazyStage = false;
+  q.lazyDone = false; q.lazyStage = false; q.sweep2Done = false;
   if (q.wide) {
     // The reads the launch above deferred. Since round 5 a fresh heavy read is recognised on the host a round ahead and starts on the
     // second stream, so the query kernel defers a read in one whole-query round of twenty (config C2: 2 434 of 42 654): the five kernels
@@ -2120,6 +2127,43 @@ int aqEnd(t4_ctx *c, AqResult *res) {
         continue;
       }
     }
+    if (q.wide && q.skipRepeats && !q.sweep2Done) {
+      // First passes of skipRepeats queries that ended without a raw overlap (wideMergeKernel queued their reads): the plain pass of
+      // GetOverlapsFromRead (SeqSet.hpp:1533-1556) as a second sweep of the wide kernels -- seed stage of the queued reads of both halves
+      // into fresh slots of half 0, the five kernels from those slots on, the extensions of the new records. One such sweep per attempt.
+      q.sweep2Done = true;
+      const int *ctl0 = (const int *)(c->aqOutHost + q.pWctl), *ctlA0 = (const int *)(c->aqOutHost + q.pWctlA);
+      const int nq0 = ctl0[4], nqA = ctlA0[4];
+      if (nq0 + nqA > 0 && !ctl0[2] && !ctlA0[2]) {
+        T4Wide w, wa;
+        memcpy(&w, c->aqInHost + q.oWide, sizeof w);
+        memcpy(&wa, c->aqInHost + q.oWideA, sizeof wa);
+        const int *list0 = w.requeue, *listA = wa.requeue;
+        w.firstRead = ctl0[0]; w.firstPart = ctl0[1];
+        const int recsBefore = (int)*(const unsigned *)(c->aqOutHost + pTail + 24);
+        const int cus = c->cus > 0 ? c->cus : 1;
+        auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; };
+        const int nq = nq0 + nqA;
+        const int gParts = clampi(2 * c->wideRecentParts + 4 * nq + 4, 4, cus * 2), gReads = clampi(nq, 1, cus < 64 ? cus : 64);
+        q.lazyStage = true;
+        HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+        if (nq0 > 0) hipLaunchKernelGGL(t4k::wideSeedKernel, dim3(nq0 < cus ? nq0 : cus), dim3(512), 0, c->stream, q.base, bv, wk, qa, w, list0, nq0, 0);
+        if (nqA > 0) hipLaunchKernelGGL(t4k::wideSeedKernel, dim3(nqA < cus ? nqA : cus), dim3(512), 0, c->stream, q.base, bv, wk, qa, w, listA, nqA, 0);
+        hipLaunchKernelGGL(t4k::wideScatterKernel, dim3(clampi(8 * gParts, 16, cus * 8)), dim3(256), 0, c->stream, q.base, w);
+        hipLaunchKernelGGL((t4k::wideSortKernel<8192>), dim3(gParts), dim3(512), 0, c->stream, q.base, w);
+        hipLaunchKernelGGL(t4k::wideStatsKernel, dim3(gReads), dim3(512), 0, c->stream, q.base, w);
+        hipLaunchKernelGGL((t4k::wideChainKernel<8192, 1 << T4_WIDE_OVBITS>), dim3(gParts < cus ? gParts : cus), dim3(512), 0, c->stream, q.base, bv, wk, qa, w);
+        hipLaunchKernelGGL(t4k::wideMergeKernel, dim3(gReads), dim3(512), 0, c->stream, q.base, bv, wk, qa, w);
+        HIPCHK(c, hipGetLastError());
+        if (q.extendLater) {
+          hipLaunchKernelGGL(t4k::extendKernel, dim3(c->cus * 16), dim3(64), 0, c->stream, q.base, bv, qa, recsBefore < c->aqPoolCap ? recsBefore : c->aqPoolCap);
+          HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+        if ((r = aqLaunchEpilogue(c))) return r;
+        continue;
+      }
+    }
     int overflow = *(int *)(c->aqOutHost + pTail);
     { const int inKernel = *(int *)(c->aqOutHost + pTail + 8); if (!smallFirst && inKernel > 0) { c->aqGlobalReads += inKernel; ++c->aqGlobalLaunches; } }
     c->aqSecFirst += tSince(q.tf0);
@@ -2177,7 +2221,7 @@ int aqEnd(t4_ctx *c, AqResult *res) {
         if (flags & 2) {
           const int need = ctl[1] > ctlA[1] ? ctl[1] : ctlA[1];
           if (need <= c->wide.maxPart) return fail(c, T4_ERR_UNSUPPORTED, "a read of this batch needs more than %d partitions of %d k-mer hits", T4_WIDE_MAXP, c->wide.pcap);
-          if ((r = ensureWide(c, n, need, 1))) return r;
+          if ((r = ensureWide(c, q.nWideSlots, need, 1))) return r;
         }
         for (int b = 0; b < 6; ++b) if (flags & (1 << b)) ++c->wideFlagCounts[b];
         if (flags & (4 | 8)) {
@@ -2188,18 +2232,28 @@ int aqEnd(t4_ctx *c, AqResult *res) {
           // one contig range) -- finer partitions for this call only.
           if (flags & 4) { c->wideSafetyKeep = q.wideSafety < 128 ? q.wideSafety : 128; c->wideCallsSinceRepeat = 0; }
         }
-        if (flags & 16) { if ((r = ensureWide(c, n, 1, ctl[3] > ctlA[3] ? ctl[3] : ctlA[3]))) return r; }
+        if (flags & 16) { if ((r = ensureWide(c, q.nWideSlots, 1, ctl[3] > ctlA[3] ? ctl[3] : ctlA[3]))) return r; }
         ++c->wideRetries; ++q.attempt;
         if ((r = aqLaunch(c))) return r;
         continue;
       }
-      c->wideReads += ctl[0] + ctlA[0]; c->wideParts += ctl[1] + ctlA[1]; c->wideGroups += ctl[3] + ctlA[3];
+      // (slots of first passes that found nothing were retired, T4WidePlan::read < 0: their partitions and dependency records are not counted)
+      int retiredParts[2] = {0, 0}, retiredGroups = 0;
+      if (ctl[4] + ctlA[4] > 0) {
+        for (int hlf = 0; hlf < 2; ++hlf) {
+          const T4WidePlan *pl = (const T4WidePlan *)(o + (hlf ? q.pWplanA : q.pWplan));
+          const int *st = (const int *)(o + (hlf ? q.pWstatA : q.pWstat));
+          const int nw = (hlf ? ctlA[0] : ctl[0]) < q.nWideSlots ? (hlf ? ctlA[0] : ctl[0]) : q.nWideSlots;
+          for (int w2 = 0; w2 < nw; ++w2) if (pl[w2].read < 0) { retiredParts[hlf] += pl[w2].P; retiredGroups += st[(size_t)w2 * T4_WIDE_STAT + WS_GROUPS]; }
+        }
+      }
+      c->wideReads += ctl[0] + ctlA[0] - ctl[4] - ctlA[4]; c->wideParts += ctl[1] + ctlA[1] - retiredParts[0] - retiredParts[1]; c->wideGroups += ctl[3] + ctlA[3] - retiredGroups;
       ++c->wideCalls; if (ctl[0] > 0) ++c->wideCallsDeferred; if (ctlA[0] > 0) ++c->wideCallsDirect;
       if (ctl[0] + ctlA[0] > 0 && ++c->wideCallsSinceRepeat >= 2048 && c->wideSafetyKeep > 32) { c->wideSafetyKeep /= 2; c->wideCallsSinceRepeat = 0; }
-      c->wideRecentParts = ctl[1] > c->wideRecentParts ? ctl[1] : (c->wideRecentParts * 7 + ctl[1]) / 8;
+      { const int parts = ctl[1] - retiredParts[0]; c->wideRecentParts = parts > c->wideRecentParts ? parts : (c->wideRecentParts * 7 + parts) / 8; }
       if (q.tierHint) {   // remembered by the caller: these reads start on the second stream the next time they are queried
         const T4WidePlan *plans[2] = {(const T4WidePlan *)(o + q.pWplan), (const T4WidePlan *)(o + q.pWplanA)};
-        const int cnt[2] = {ctl[0] < n ? ctl[0] : n, ctlA[0] < n ? ctlA[0] : n};
+        const int cnt[2] = {ctl[0] < q.nWideSlots ? ctl[0] : q.nWideSlots, ctlA[0] < q.nWideSlots ? ctlA[0] : q.nWideSlots};
         for (int hlf = 0; hlf < 2; ++hlf) for (int w2 = 0; w2 < cnt[hlf]; ++w2) if (plans[hlf][w2].read >= 0 && plans[hlf][w2].read < n) q.tierHint[plans[hlf][w2].read] = 1;
       }
     }
@@ -2366,7 +2420,7 @@ int t4_add_query_groups(t4_ctx *c, int i, const t4_grp **groups, int *n, int *hu
     const int *ctl = (const int *)(o + (half ? q.pWctlA : q.pWctl));
     const T4WidePlan *plan = (const T4WidePlan *)(o + (half ? q.pWplanA : q.pWplan));
     const int *stat = (const int *)(o + (half ? q.pWstatA : q.pWstat));
-    const int nw = ctl[0] < q.n ? ctl[0] : q.n;
+    const int nw = ctl[0] < q.nWideSlots ? ctl[0] : q.nWideSlots;
     for (int w = 0; w < nw; ++w) {
       if (plan[w].read != i) continue;
       *groups = (const t4_grp *)c->grpPoolHost + (half ? (size_t)c->wide.grpCap : 0) + plan[w].grpBase;

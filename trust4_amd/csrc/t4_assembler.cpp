@@ -671,6 +671,13 @@ struct t4_assembler : IndexListener {
     // those of an entry that holds a result; `killed` = one of them invalidated it (the result is dropped when it arrives),
     // `shifts` = left extensions of contigs it meets, to be applied to the records when they arrive
     bool inflight = false, killed = false;
+    // An entry with skip (repetitive data) stands under the rule of a cell's window, whichever route served it: any commit that changes
+    // the index or a contig ends it. Its answer may come from the plain pass, which reads lists of 100 or more postings (the first and
+    // the last k-mer, one emitted after k / 2 passed over), while the host's record of its emitted positions (emitMask, buildGroups) is
+    // the first pass's: an edit of such a list would pass it by. An entry with a barcode and without skip that the WIDE query served
+    // stands under the same rule (`conservative`); one whose query was out when such a commit came (`sawCommit`) is dropped when the
+    // records say that the wide query served it. Barcoded entries the single-workgroup tiers serve keep their rules.
+    bool conservative = false, sawCommit = false;
     std::vector<std::pair<int, int>> shifts;
     bool standing() const { return valid || partial || (inflight && !killed); }
   };
@@ -1788,31 +1795,40 @@ int t4_assembler::emittedHits(Cached &e) {
   memset(e.emitMask, 0, sizeof e.emitMask);
   e.maskOk = len - k + 1 <= T4_MAX_READ_KMERS;
   if (len < k) return 0;
-  int64_t H = 0;
-  bool huge = false;
-  uint64_t prev = 0;
-  for (int st = 0; st < 2; ++st) {
-    if (st == 0 ? e.strand == -1 : e.strand == 1) continue;
-    const std::string &r = st ? rcs : e.read;
-    KCode kc(k);
-    int skipCnt = 0;
-    for (int i = 0; i < len; ++i) {
-      kc.append(r[i]);
-      if (i < k - 1) continue;
-      if (i == k - 1 || prev != kc.code) {
-        const ListRef *l = kc.valid() ? index.find(kc.code, index.bucket(kc.code, e.barcode)) : nullptr;
-        const uint32_t size = l ? l->cnt : 0;
-        if (size >= 100 && i != k - 1 && i != len - 1 && skipCnt < skipLimit) { ++skipCnt; continue; }
-        if (size >= 100 && e.skip) continue;   // allowTotalSkip (repetitive data, --trimLevel 2: SeqSet.hpp:1392-1393)
-        skipCnt = 0;
-        if (e.maskOk) e.emitMask[st][(i - k + 1) >> 6] |= 1ull << ((i - k + 1) & 63);   // looked up, not passed over (Cached::emitMask)
-        H += size;
-        if (size > 10000) huge = true;   // a list beyond 10000 postings: the wide query whatever the total (removeOnlyRepeats)
+  const auto pass = [&](bool totalSkip) {
+    int64_t H = 0;
+    bool huge = false;
+    uint64_t prev = 0;
+    memset(e.emitMask, 0, sizeof e.emitMask);
+    for (int st = 0; st < 2; ++st) {
+      if (st == 0 ? e.strand == -1 : e.strand == 1) continue;
+      const std::string &r = st ? rcs : e.read;
+      KCode kc(k);
+      int skipCnt = 0;
+      for (int i = 0; i < len; ++i) {
+        kc.append(r[i]);
+        if (i < k - 1) continue;
+        if (i == k - 1 || prev != kc.code) {
+          const ListRef *l = kc.valid() ? index.find(kc.code, index.bucket(kc.code, e.barcode)) : nullptr;
+          const uint32_t size = l ? l->cnt : 0;
+          if (size >= 100 && i != k - 1 && i != len - 1 && skipCnt < skipLimit) { ++skipCnt; continue; }
+          if (size >= 100 && totalSkip) continue;   // allowTotalSkip (repetitive data, --trimLevel 2: SeqSet.hpp:1392-1393)
+          skipCnt = 0;
+          if (e.maskOk) e.emitMask[st][(i - k + 1) >> 6] |= 1ull << ((i - k + 1) & 63);   // looked up, not passed over (Cached::emitMask)
+          H += size;
+          if (size > 10000) huge = true;   // a list beyond 10000 postings: the wide query whatever the total (removeOnlyRepeats)
+        }
+        prev = kc.code;
       }
-      prev = kc.code;
     }
-  }
-  return huge || H > 0x7FFFFFFF ? 0x7FFFFFFF : (int)H;
+    return huge || H > 0x7FFFFFFF ? (int64_t)0x7FFFFFFF : H;
+  };
+  if (!e.skip) return (int)pass(false);
+  // A skip entry: the count of the pass that DECIDES. A first pass of fewer than three hits cannot hold a run of three (the
+  // threshold of filter 0), so it is empty and the plain pass follows: its count. Otherwise the first pass's own count -- it is handed
+  // over by that count, and whether it comes back empty only the query knows (such a read's plain pass is recognised at harvest).
+  const int64_t h1 = pass(true);
+  return (int)(h1 < 3 ? pass(false) : h1);
 }
 
 // Hits of the read per (strand, contig) against the current index (host replica; read-only here): the number of hits, and the
@@ -1922,6 +1938,14 @@ void t4_assembler::processEvents() {
     else if (e.inflight && !e.killed) { e.killed = true; ++invalidations; ++why; }
   };
   // what the entry's result takes from contig c falls: when the entry qualifies (Cached: restricted re-query) it keeps the rest
+  // every entry with skip, and the barcoded entries the wide query served, fall with any commit that left an event (Cached::conservative)
+  for (int sl : order) {
+    Cached &e = *pool[sl];
+    if (!e.standing() || !(e.skip || e.barcode != -1)) continue;
+    if (e.skip) { kill(e, invContig); continue; }
+    if (e.inflight && !e.killed) e.sawCommit = true;
+    if (e.valid && e.conservative) kill(e, invContig);
+  }
   auto touch = [&](Cached &e, int c, int64_t &why) {
     if (e.partial) {
       if (!e.isPending(c)) {
@@ -2141,7 +2165,7 @@ void t4_assembler::announceLive(int n, const char *const *reads, const int *stra
     c.inflight = false; c.killed = false; c.shifts.clear();
     c.ov.clear(); c.ext.clear(); c.extRet.clear();
     c.uid = nextUid++; c.tier = 0; c.hintPredicted = false; c.lastUs = 0; c.registered = false; c.lastKill = 0;
-    c.hasDev = false; c.hostRecords = false; c.expectWide = false; c.devGroups.clear(); c.dbgGroups.clear(); c.devInfo.clear(); c.rorOk = false; c.editedKeys.clear();
+    c.hasDev = false; c.hostRecords = false; c.expectWide = false; c.conservative = false; c.sawCommit = false; c.devGroups.clear(); c.dbgGroups.clear(); c.devInfo.clear(); c.rorOk = false; c.editedKeys.clear();
     c.partial = false; c.pendingContig = -1; c.merged = false; c.auxOk = false; c.restrictedCount = 0; c.kmerPos.clear();
     c.cands.clear(); c.candOk = false; c.exactKeys.clear(); c.morePending.clear(); c.inexact = false; c.repeatNear = false; c.checkPending = false; c.maskOk = false;
     order.push_back(sl);
@@ -2177,7 +2201,7 @@ int t4_assembler::launchOn(Lane &L, const std::vector<int> &todo, int repetitive
     c.inflight = true; c.killed = false; c.shifts.clear();
     if (c.partial) { anyOnly = true; continue; }   // restricted re-query: the entry keeps what it holds of the other contigs
     c.statsStable = false;
-    c.hasDev = false; c.hostRecords = false; c.expectWide = false; c.devGroups.clear(); c.dbgGroups.clear(); c.devInfo.clear(); c.rorOk = false; c.editedKeys.clear();
+    c.hasDev = false; c.hostRecords = false; c.expectWide = false; c.conservative = false; c.sawCommit = false; c.devGroups.clear(); c.dbgGroups.clear(); c.devInfo.clear(); c.rorOk = false; c.editedKeys.clear();
     c.auxOk = false; c.merged = false; c.restrictedCount = 0;
     c.cands.clear(); c.candOk = false; c.exactKeys.clear();
   }
@@ -2223,9 +2247,14 @@ int t4_assembler::launchOn(Lane &L, const std::vector<int> &todo, int repetitive
       if (e.partial) continue;   // (its group of the one contig is rebuilt when the records arrive)
       // a read whose emitted hits outgrow the LDS tier is served by the wide query, which returns its dependency records itself
       // (deriving them here would cost several times the query: every posting of every k-mer, the ones the repeat-skip rule passes over included)
-      if (wideQueries && !repetitive && e.barcode == -1 && emittedHits(e) > wideHitLimit) {
+      // (an entry with skip: emittedHits counts the pass that decides as far as the host can tell -- the plain pass when the first emits
+      // fewer than three hits, else the first, which the query kernel hands over by the same count; a plain pass that goes wide after a
+      // first pass of three or more hits that chained nothing is recognised at harvest by the records that come back. An entry with
+      // a barcode: the count before the barcode filter, which is what the query kernel decides on.)
+      if (wideQueries && emittedHits(e) > wideHitLimit) {
         // (T4_VERIFY_WINDOW: the host's replay of the emitted hits is derived all the same and held against the wide query's records when they arrive)
-        if (knobs.verifyWindow) { buildGroups(e); e.dbgGroups.swap(e.devGroups); e.devGroups.clear(); e.hasDev = false; e.hostRecords = false; }
+        // (not for a skip entry: which of its passes decides is the query's to know)
+        if (knobs.verifyWindow && !e.skip) { buildGroups(e); e.dbgGroups.swap(e.devGroups); e.devGroups.clear(); e.hasDev = false; e.hostRecords = false; }
         e.expectWide = true; e.groups.reset(16); e.slack = -1; e.fragile = true;
       }
       else buildGroups(e);
@@ -2238,11 +2267,11 @@ int t4_assembler::launchOn(Lane &L, const std::vector<int> &todo, int repetitive
   // it is now; it is a hint: either path serves any read.
   std::vector<int> predict;
   std::atomic<int> nextP(0);
-  if (wideQueries && !repetitive && mi > 0 && !anyOnlyAll) {
+  if (wideQueries && mi > 0 && !anyOnlyAll) {
     size_t seen = 0;
     for (size_t i = 0; i < order.size() && seen < 48; ++i) {
       Cached &e = *pool[order[i]];
-      if (e.valid || e.inflight || e.partial || e.hintPredicted || e.tier || e.lastUs || e.barcode != -1) continue;
+      if (e.valid || e.inflight || e.partial || e.hintPredicted || e.tier || e.lastUs) continue;
       predict.push_back(order[i]); ++seen;
     }
   }
@@ -2751,6 +2780,7 @@ int t4_assembler::harvest(Lane &L) {
           c.dbgGroups.clear();
         }
         c.hasDev = true; c.hostRecords = false; c.groups.reset(16);
+        c.conservative = c.skip || c.barcode != -1;
         c.slack = 99 - n4; c.fragile = huge != 0;
         c.inexact = false; c.editedKeys.clear();
         if (huge && c.candOk) {   // removeOnlyRepeats as this query found it, from its own records (exactStats repeats the loop the kernel ran)
@@ -2761,6 +2791,9 @@ int t4_assembler::harvest(Lane &L) {
       } else if (c.expectWide) { buildGroups(c); ++wideMispredicted; }   // (the LDS tier served it after all)
       c.expectWide = false;
     }
+    const bool staleWide = c.conservative && c.sawCommit;   // (a commit came while the query of a wide-served barcoded entry was out)
+    c.sawCommit = false;
+    if (staleWide) { c.lastKill = 5; ++invalidations; ++invContig; ++killedInFlight; continue; }   // (Cached::conservative: a commit came while its query was out)
     c.valid = true;
   }
   ts.lap(TS_HARVEST_COPY);
@@ -3086,6 +3119,7 @@ int t4_assembler_live_counters(const t4_assembler *a, int64_t *out, int n) {
   for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
   if (n >= 23) t4_add_query_stats(a->ctx, out + 16);
   if (n >= 27) t4_add_query_wide_stats(a->ctx, out + 23);   // the wide query: reads it served, partitions, calls repeated with larger pools, dependency records
+  if (n >= 28) out[27] = a->wideServed;   // window entries whose whole query the wide query served (all lanes)
   if (getenv("T4_VERIFY_WINDOW")) fprintf(stderr, "T4_VERIFY_WINDOW: the host's replay of the emitted hits equals the wide query's dependency records for all %lld reads it was held against\n", (long long)a->groupSelfChecks);
   if (getenv("T4_VERIFY_WINDOW")) fprintf(stderr, "T4_VERIFY_WINDOW: %lld served window entries queried again at serve time, all equal to their cached results (%lld of them put together from restricted re-queries)\n", (long long)a->verified, (long long)a->verifiedMerged);
   if (getenv("T4_TIMING")) {

@@ -94,13 +94,18 @@ struct T4TierCaps { int cap[T4_NTIER - 1]; };   // hit capacity of the LDS tiers
 // replayed over the partitions' records by one workgroup per read.
 struct T4Grp { unsigned key; unsigned cnt; int lo, hi; };   // dependency set of a query: key = contig * 2 + (strand == 1); hits; hull of the diagonals with >= 3 hits (lo > hi: none)
 #define T4_WIDE_MAXP 2048     // partitions of one read (11 bits of the merge's record index)
-struct T4WidePlan { int pBase, P, Wd /* unused since the partitions follow the hits' distribution */, nk; unsigned H; int huge /* a list beyond 10000 postings */, read, grpBase; };
+struct T4WidePlan { int pBase, P, pass /* 1: the first pass of a skipRepeats query (allowTotalSkip, filter 0); 0: the plain pass */, nk; unsigned H /* emitted postings, before the barcode filter */;
+                    int huge /* a list beyond 10000 postings (never in a first pass, never for a barcoded read: its hits all count repeats = 1) */, read /* -1 - read: a first pass that found nothing, queued again */, grpBase;
+                    int barcode /* -1, or the only contig barcode whose postings are hits (an index that is not keyed by barcode) */; };
 #define T4_WIDE_STAT 24      // ints per read: see wideStatsKernel
 struct T4Wide {
   int enabled;
   int maxReads, maxPart, pcap, maxOvPart, safetyNum /* partitions are planned for pcap * 16 / safetyNum hits */, maxPartPerRead;
   int minHits;               // a read goes wide when its seed stage emits more hits than this (or meets a list beyond 10000 postings, or outgrows the global-scratch tier)
-  int *ctl;                  // [0] reads, [1] partitions, [2] overflow flags (1 reads, 2 partitions, 4 keys of a partition, 8 overlaps of a partition, 16 group pool), [3] group pool cursor
+  int firstRead, firstPart;  // the kernels behind the seed stage start at this read slot / partition (second sweep: the slots before are done)
+  int *ctl;                  // [0] reads, [1] partitions, [2] overflow flags (1 reads, 2 partitions, 4 keys of a partition, 8 overlaps of a partition, 16 group pool), [3] group pool cursor,
+                             // [4] first passes that ended without a raw overlap: their reads wait in `requeue` for a second sweep as plain passes
+  int *requeue;              // [maxReads]
   T4WidePlan *plan;          // [maxReads]
   uint2 *seed;               // [maxReads][2 * T4_MAXL]: (start, emitted postings) of every k-mer position, forward strand first
   int *bounds;               // [maxReads][T4_WIDE_MAXP + 1]: first contig of every partition of a read (quantiles of a sample of its hits' contigs)

@@ -2443,8 +2443,9 @@ __device__ int seedChainPass(const T4IndexView &ix, WaveMem &wm, WaveState *ws, 
     for (int q = lane; q < 2 * nk; q += NT) if (posPref[q + 1] - posPref[q] > 10000u) huge = 1;
     if (blockSum(huge, ws->red)) { if (NOVEL && ws->wideWant) return -3; if (lane == 0) ws->unsupported = 1; }
   }
-  if (NOVEL && ws->wideWant && H > ws->wideWant && !allowTotalSkip && !vjOnly && filter == 1) return -3;   // heavy enough for the wide query (t4_wide.h)
-  if (H > wm.hitLimit) return (NOVEL && ws->wideWant && !wm.ldsArrays && !allowTotalSkip && !vjOnly && filter == 1) ? -3 : -1;
+  // (the first pass of a skipRepeats query -- allowTotalSkip, filter 0 -- is handed over like the plain one; the caller tells them apart)
+  if (NOVEL && ws->wideWant && H > ws->wideWant && !vjOnly && (filter == 1 || allowTotalSkip)) return -3;   // heavy enough for the wide query (t4_wide.h)
+  if (H > wm.hitLimit) return (NOVEL && ws->wideWant && !wm.ldsArrays && !vjOnly && (filter == 1 || allowTotalSkip)) ? -3 : -1;
   PHASE_MARK(ws, 2);
 #if T4_OPT_KEY32
   const int k32 = ix.key32;
@@ -2771,7 +2772,8 @@ __device__ __forceinline__ bool scoreOverlaps(const T4IndexView &ix, WaveMem &wm
 
 // SeqSet::GetOverlapsFromRead (SeqSet.hpp:1508-2124, readType 0) for the segment in wm.seg / wm.rc.
 // Scored and filtered overlaps are appended to wm.fin (coordinates shifted by `shift`).
-// Returns the reference's return value (-1, 0 or the overlap count); -2 on capacity overflow.
+// Returns the reference's return value (-1, 0 or the overlap count); -2 on capacity overflow; -3 / -4: the plain pass / the first pass
+// of a skipRepeats query is for the wide query (seedChainPass; after an empty first pass the hand-over is -3: that pass is done).
 // ROWS: the row-per-overlap finishing pass for short lists (the AddRead / AssignRead kernels; the rough-annotation kernels, whose
 // overlaps are reference genes, keep their register budget).
 template <bool ROWS>
@@ -2802,7 +2804,7 @@ __device__ int overlapsFromSegment(const T4IndexView &ix, WaveMem &wm, WaveState
   }
   if (skipRepeats) {
     int H = seedChainPass<ROWS>(ix, wm, ws, segLen, strandArg, barcode, true, false, ix.hitLenRequired, 0);
-    if (H < 0) return -2;
+    if (H < 0) return H == -3 ? -4 : -2;
     hitTotal += (unsigned long long)H;
     __syncthreads();
     overlapCnt = ws->ovCount;
@@ -3604,7 +3606,8 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
     int barcode = bv.barcode ? bv.barcode[r] : -1;
     // a pass that outgrows this workgroup's arrays (hits or overlaps) is spread over the chip: the wide query (t4_wide.h)
     const int onlySeq = qa.onlySeq ? qa.onlySeq[r] : -1;
-    const bool wide = onlySeq < 0 && wk.wide != nullptr && !qa.skipRepeats && barcode == -1 && ix.hasNovel == 2 && !qa.views && qa.extendLater > 0;
+    // (either pass of a skipRepeats query, barcoded reads too; an index keyed by barcode keeps its barcoded reads on this workgroup)
+    const bool wide = onlySeq < 0 && wk.wide != nullptr && (barcode == -1 || !ix.considerBarcode) && ix.hasNovel == 2 && !qa.views && qa.extendLater > 0;
     if (lane == 0) ws->wideWant = wide ? (wk.wide->minHits > 0 ? wk.wide->minHits : 1) : 0;
     if (lane == 0 && qa.cs) {
       const T4CandArgs *cs = qa.cs;
@@ -3618,12 +3621,13 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
       return true;
     }
     if (lane == 0 && onlySeq < 0) {
-      if (qa.aux) qa.aux[r] = (ret == -2 || ret == -3) ? -1 : ((ws->nAll > 32767 ? 32767 : ws->nAll) | (((ws->nOther > 32767 || ws->vjRescue) ? 32767 : ws->nOther) << 15) | (ws->strand0 << 30));   // (a VJ-rescue result reads as "overlaps on the other strand": never eligible for a restricted re-query)
+      if (qa.aux) qa.aux[r] = (ret <= -2) ? -1 : ((ws->nAll > 32767 ? 32767 : ws->nAll) | (((ws->nOther > 32767 || ws->vjRescue) ? 32767 : ws->nOther) << 15) | (ws->strand0 << 30));   // (a VJ-rescue result reads as "overlaps on the other strand": never eligible for a restricted re-query)
       if (qa.n4) qa.n4[r] = ws->nvN4[0] + ws->nvN4[1];
     }
-    if (wide && (ret == -3 || (ret == -2 && !wm.ldsArrays))) {   // (overlaps beyond the LDS tier's arrays: the global-scratch pass of this workgroup first)
+    if (wide && (ret == -3 || ret == -4 || (ret == -2 && !wm.ldsArrays))) {   // (overlaps beyond the LDS tier's arrays: the global-scratch pass of this workgroup first)
       hitTotal = 0;   // (the pass is counted by the wide query's seed stage)
-      wideDeferRead(ix, wm, ws, *wk.wide, len, qa.strandPerRead[r], r, hitTotal);
+      // (-2 does not say which pass outgrew the arrays: a skipRepeats query starts again at its first)
+      wideDeferRead(ix, wm, ws, *wk.wide, len, qa.strandPerRead[r], r, hitTotal, (ret == -4 || (ret == -2 && qa.skipRepeats)) ? 1 : 0, barcode);
       if (lane == 0) atomicAdd(wk.hitCounter, hitTotal);
       return true;
     }

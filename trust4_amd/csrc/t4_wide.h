@@ -28,19 +28,22 @@
 #define T4_WIDE_PART_SAMPLES 256   // hits sampled per planned partition for its boundaries (at least 512, at most 4 096 per read: profiles/r06g)
 
 // ws->red[13..15] are free for this (the scans use the first eight words)
+// pass 1: the first pass of a skipRepeats query (GetHitsFromRead with allowTotalSkip: no list of 100 or more postings is emitted);
+// barcode: of the read, -1 none (the index is not keyed by barcode: postings of contigs with another barcode are dropped by the scatter)
 __device__ T4_NI void wideDeferRead(const T4IndexView &ix, WaveMem &wm, WaveState *ws, const T4Wide &wd, int len, int strandArg, long long r,
-                                    unsigned long long &hitTotal) {
+                                    unsigned long long &hitTotal, int pass, int barcode) {
   const int lane = tid(), NT = nthr();
   unsigned *posStart = (unsigned *)wm.ov, *posPref = wm.pairs;
   const int nk = len - ix.k + 1;
   __syncthreads();
-  const int H = seedPositionsNovel(ix, wm, len, strandArg, -1, false, posStart, posPref, ws->red, wm.keys, (WaveState *)0);
+  const int H = seedPositionsNovel(ix, wm, len, strandArg, barcode, pass == 1, posStart, posPref, ws->red, wm.keys, (WaveState *)0);   // (the partitions are planned for the hits before the barcode filter: an upper bound)
   hitTotal += (unsigned long long)H;
   int huge = 0;
-  for (int q = lane; q < 2 * nk; q += NT) if (posPref[q + 1] - posPref[q] > 10000u) huge = 1;
+  // (a barcoded read's hits all carry repeats = 1, SeqSet.hpp:1406-1407: removeOnlyRepeats and the run test never fire for it, however long the list)
+  if (barcode == -1) for (int q = lane; q < 2 * nk; q += NT) if (posPref[q + 1] - posPref[q] > 10000u) huge = 1;
   huge = blockSum(huge, ws->red) != 0;
   if (lane == 0) {
-    int slot = atomicAdd(&wd.ctl[0], 1), pBase = 0, P = 0, Wd = 1;
+    int slot = atomicAdd(&wd.ctl[0], 1), pBase = 0, P = 0;
     if (slot >= wd.maxReads) { atomicOr(&wd.ctl[2], 1); slot = -1; }
     else {
       const long long per = 16LL * wd.pcap;
@@ -55,7 +58,7 @@ __device__ T4_NI void wideDeferRead(const T4IndexView &ix, WaveMem &wm, WaveStat
         if (pBase + P > wd.maxPart) { atomicOr(&wd.ctl[2], 2); P = 0; }
       }
       T4WidePlan pl;
-      pl.pBase = pBase; pl.P = P; pl.Wd = Wd; pl.nk = nk; pl.H = (unsigned)H; pl.huge = huge; pl.read = (int)r; pl.grpBase = 0;
+      pl.pBase = pBase; pl.P = P; pl.pass = pass == 1 ? 1 : 0; pl.barcode = barcode; pl.nk = nk; pl.H = (unsigned)H; pl.huge = huge; pl.read = (int)r; pl.grpBase = 0;
       wd.plan[slot] = pl;
     }
     ws->red[15] = slot; ws->red[14] = pBase; ws->red[13] = P;
@@ -100,7 +103,9 @@ __device__ T4_NI void wideDeferRead(const T4IndexView &ix, WaveMem &wm, WaveStat
 
 // Reads known to be heavy (the window entry's last query was served wide) skip the LDS tier: their seed stage runs here, on a
 // second stream, and the wide kernels behind it run BESIDE the round's query kernel instead of after it.
-__global__ __launch_bounds__(512) void wideSeedKernel(T4IndexView ixArg, T4BatchView bvArg, T4Work wk, T4QueryArgs qa, T4Wide wd, const int *list, int nList) {
+// pass: 1 the reads start with the first pass of a skipRepeats query, 0 with the plain pass (also the second sweep of the reads whose
+// first pass found nothing: list = T4Wide::requeue)
+__global__ __launch_bounds__(512) void wideSeedKernel(T4IndexView ixArg, T4BatchView bvArg, T4Work wk, T4QueryArgs qa, T4Wide wd, const int *list, int nList, int pass) {
   __shared__ unsigned long long s_code[2048];   // k-mer codes of the seed stage, then the sample of the hits' contigs (4096 x u32)
   __shared__ unsigned s_pref[2 * T4_MAXL + 2];
   __shared__ unsigned s_start[2 * T4_MAXL + 2];
@@ -128,7 +133,7 @@ __global__ __launch_bounds__(512) void wideSeedKernel(T4IndexView ixArg, T4Batch
     if (len < s_ix.k) { if (threadIdx.x == 0) qa.counts[r] = -1; continue; }   // (GetOverlapsFromRead's own answer: no k-mer)
     loadSegment(s_bv, r, 0, len, s_wm);
     unsigned long long hitTotal = 0;
-    wideDeferRead(s_ix, s_wm, &s_ws, s_wd, len, qa.strandPerRead[r], r, hitTotal);
+    wideDeferRead(s_ix, s_wm, &s_ws, s_wd, len, qa.strandPerRead[r], r, hitTotal, pass, s_bv.barcode ? s_bv.barcode[r] : -1);
     if (threadIdx.x == 0) atomicAdd(wk.hitCounter, hitTotal);
   }
 }
@@ -152,7 +157,7 @@ __global__ __launch_bounds__(256) void wideScatterKernel(T4IndexView ix, T4Wide 
     __syncthreads();
     if (lane == 0) {   // which read, which of its chunks (a few dozen reads at most: a walk)
       unsigned left = item;
-      int w = 0;
+      int w = wd.firstRead;
       for (; w < nR; ++w) {
         const T4WidePlan pw = wd.plan[w];
         const unsigned nCh = pw.P > 0 ? (pw.H + T4_WIDE_CH - 1u) / T4_WIDE_CH : 0u;
@@ -176,6 +181,7 @@ __global__ __launch_bounds__(256) void wideScatterKernel(T4IndexView ix, T4Wide 
       __syncthreads();
     }
     const unsigned s0 = chunk * T4_WIDE_CH, end = s0 + T4_WIDE_CH < pl.H ? s0 + T4_WIDE_CH : pl.H;
+    const int bc = pl.barcode;   // (one read per work item: uniform over the workgroup)
     unsigned long long key[4];
     int part[4];
 #pragma unroll
@@ -193,6 +199,8 @@ __global__ __launch_bounds__(256) void wideScatterKernel(T4IndexView ix, T4Wide 
         int plo = 0, phi = pl.P - 1;   // last partition whose first contig is <= this one
         while (plo < phi) { const int mid = (plo + phi + 1) >> 1; if (s_bound[mid] <= po.x) plo = mid; else phi = mid - 1; }
         part[t] = plo;
+        // a posting of a contig with another barcode is not a hit (SeqSet.hpp:1418, 1485): dropped before anything counts it
+        if (bc != -1 && ix.seqs[po.x].barcode != bc) part[t] = -1;
       }
     }
     // one atomic per (wavefront, partition) instead of one per posting: consecutive postings of a list belong to neighbouring
@@ -229,7 +237,7 @@ __global__ __launch_bounds__(512) void wideSortKernel(T4IndexView ix, T4Wide wd)
   __shared__ int s_red[16];
   if (wd.ctl[2]) return;
   const int nPart = wideParts(wd), lane = threadIdx.x, NT = blockDim.x;
-  for (int pg = blockIdx.x; pg < nPart; pg += gridDim.x) {
+  for (int pg = wd.firstPart + blockIdx.x; pg < nPart; pg += gridDim.x) {
     const int w = wd.pRead[pg];
     const T4WidePlan pl = wd.plan[w];
     const int n = (int)wd.pCnt[pg];
@@ -299,7 +307,7 @@ __global__ __launch_bounds__(512) void wideStatsKernel(T4IndexView ix, T4Wide wd
   __shared__ unsigned s_cnt[T4_WIDE_SEEDS];
   if (wd.ctl[2]) return;
   const int nR = wideReads(wd), lane = threadIdx.x, NT = blockDim.x;
-  for (int w = blockIdx.x; w < nR; w += gridDim.x) {
+  for (int w = wd.firstRead + blockIdx.x; w < nR; w += gridDim.x) {
     T4WidePlan pl = wd.plan[w];
     const int P = pl.P;
     if (P <= 0) continue;
@@ -367,7 +375,12 @@ __global__ __launch_bounds__(512) void wideStatsKernel(T4IndexView ix, T4Wide wd
     }
     __syncthreads();
     int *st = wd.stat + (size_t)w * T4_WIDE_STAT;
-    if (lane == 0) {
+    if (lane == 0 && pl.pass == 1) {
+      // GetOverlapsFromHits with filter 0 (the first pass of a skipRepeats query): the statistics loop does not run -- thresholds 3 / 3,
+      // no removeOnlyRepeats, nothing measured (what overlapsFromKeys leaves for filter 0)
+      for (int t = 0; t < T4_WIDE_STAT; ++t) st[t] = 0;
+      st[WS_NOVELMIN] = st[WS_NOVELMIN + 1] = 3; st[WS_STABLE] = 1; st[WS_GROUPS] = G; st[WS_STATS8 + 6] = st[WS_STATS8 + 7] = 3;
+    } else if (lane == 0) {
       int stable = pl.huge ? 0 : 1;
       for (int t = 0; t <= 1; ++t) {
         const int possible = s_acc[t], longest = s_acc[2 + t];
@@ -498,7 +511,7 @@ __global__ __launch_bounds__(512) void wideChainKernel(T4IndexView ixArg, T4Batc
   sc.rows = wk.dpRows + ((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * (6 * T4_ROWW * 64);
   sc.dir = wk.dpDir + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * T4_DIR_BYTES;
   const int nPart = wideParts(wd), lane = threadIdx.x, NT = blockDim.x, K = ix.k;
-  for (int pg = blockIdx.x; pg < nPart; pg += gridDim.x) {
+  for (int pg = wd.firstPart + blockIdx.x; pg < nPart; pg += gridDim.x) {
     const int w = wd.pRead[pg];
     const T4WidePlan pl = wd.plan[w];
     const int n = (int)wd.pCnt[pg];
@@ -636,7 +649,7 @@ __global__ __launch_bounds__(512) void wideMergeKernel(T4IndexView ix, T4BatchVi
   __shared__ int s_best;
   if (wd.ctl[2]) return;
   const int nR = wideReads(wd), lane = threadIdx.x, NT = blockDim.x;
-  for (int w = blockIdx.x; w < nR; w += gridDim.x) {
+  for (int w = wd.firstRead + blockIdx.x; w < nR; w += gridDim.x) {
     const T4WidePlan pl = wd.plan[w];
     const int P = pl.P;
     if (P <= 0) continue;
@@ -655,6 +668,12 @@ __global__ __launch_bounds__(512) void wideMergeKernel(T4IndexView ix, T4BatchVi
     const int N = carry;
     if (lane == 0) s_off[P] = N;
     __syncthreads();
+    if (N == 0 && pl.pass == 1) {
+      // a first pass without a raw overlap (the count of GetOverlapsFromHits, before sort and filters: SeqSet.hpp:1526-1530): the read
+      // runs the plain pass next -- queued for the host's second sweep, this slot retired
+      if (lane == 0) { const int at = atomicAdd(&wd.ctl[4], 1); if (at < wd.maxReads) wd.requeue[at] = (int)r; wd.plan[w].read = -1 - (int)r; }   // (at most one entry per slot)
+      continue;
+    }
     const int *st = wd.stat + (size_t)w * T4_WIDE_STAT;
     if (lane == 0 && qa.statsStable) qa.statsStable[r] = st[WS_STABLE];
     if (lane == 0 && qa.n4) qa.n4[r] = st[WS_N4];
