@@ -296,13 +296,15 @@ int t4_assembler_prefetch(t4_assembler *a, int n, const char *const *reads, cons
 int t4_assembler_window_valid(const t4_assembler *a);
 /* Host threads that derive the window's dependency sets while the GPU runs a query batch (default 1). */
 int t4_assembler_set_threads(t4_assembler *a, int host_threads);
-/* Counters of a set whose index is not keyed by barcode (device image by deltas, sliding window), up to 28 values:
+/* Counters of a set whose index is not keyed by barcode (device image by deltas, sliding window), up to 30 values:
  * query rounds, reads queried, deltas, delta bytes, invalidations (total; by an index change of one of the read's keys; by a
  * list crossing 100 postings; by a changed region within reach; by a left extension; by a whole-contig change; by exhausted
  * tolerance), tolerated index changes, microseconds in deltas / dependency sets / event examination / query batches; then of
  * the ctx's AddRead query path: calls, reads, launches of the global-scratch tier, reads it served, result records,
  * microseconds of its kernels (HIP events), _hit records its seed stages emitted; [23..26] of its wide query: reads served,
- * partitions, calls repeated with larger pools, dependency records; [27] window entries the wide query served (all lanes). */
+ * partitions, calls repeated with larger pools, dependency records; [27] window entries the wide query served (all lanes);
+ * [28] restricted re-queries of window entries with posting lists beyond 10000 entries that were merged (T4_FRAGILE_CHECKS);
+ * [29] window entries that fell whole to a change of one contig because they hold such lists. */
 int t4_assembler_live_counters(const t4_assembler *a, int64_t *out, int n);
 /* The chain of dependent query rounds of a live set ("the floor"): up to 10 values -- rounds; rounds that carried restricted
  * re-queries only; 5th percentile and median of a round's kernel milliseconds (HIP events); 5th percentile and median of a round's

@@ -95,6 +95,13 @@ def _load():
         "t4_cellset_update_all_consensus": (I, [P]), "t4_cellset_set_threads": (I, [P, I]), "t4_cellset_size": (I, [P]),
         "t4_cellset_output": (I, [P, C.c_char_p, P, I]), "t4_cellset_counters": (I, [P, P, P, P, P, P, P]),
         "t4_cellset_image_stats": (I, [P, P, I]),
+        # library-internal calls of the AddRead query (csrc/t4_internal.h): what a restricted re-query is driven with
+        "t4_add_query_pool_begin2": (I, [P, I, P, P, P, P, I, P, P, P, P, I]), "t4_add_query_pool_end": (I, [P] + [C.POINTER(P)] * 5),
+        "t4_add_query_last_cands": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(I)]),
+        "t4_add_query_last_aux": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(I)]),
+        "t4_add_query_head": (I, [P, I, C.POINTER(I), C.POINTER(P), C.POINTER(I)]),
+        "t4_add_query_arm_long_lists": (I, [P, I, P, P, P, I]),
+        "t4_add_query_last_long_lists": (I, [P, C.POINTER(P), C.POINTER(I)]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name) and os.environ.get("T4_LIB"):   # an older build of the library under T4_LIB (A/B timing of a kernel): the calls it lacks fail when made
@@ -205,6 +212,67 @@ class Engine:
         out = (C.c_int64 * 2)()
         self.check(self.lib.t4_assign_wide_stats(self.h, out))
         return int(out[0]), int(out[1])
+
+    def add_query_whole(self, ix, reads, strands=None, factors=None, only_seq=None, force_min=None, want_cands=1):
+        """t4_add_query_pool_begin2 + _end on this engine: whole queries, or -- only_seq[i] >= 0 -- restricted re-queries of read i
+        against that one contig (force_min[i]: novelMinHitRequired minus | plus << 16 of its last whole query). Returns a dict:
+        counts, status, stats (n x T4_QUERY_STATS words) and per read the overlap records `ov` (OV_DTYPE arrays, None when the read
+        has none)."""
+        n = len(reads)
+        buf = np.frombuffer(("".join(reads) + "\0").encode(), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(r) for r in reads])
+        st = np.zeros(n, dtype=np.int32) if strands is None else np.asarray(strands, dtype=np.int32)
+        fa = np.ones(n, dtype=np.float64) if factors is None else np.asarray(factors, dtype=np.float64)
+        only = None if only_seq is None else np.asarray(only_seq, dtype=np.int32)
+        force = None if force_min is None else np.asarray(force_min, dtype=np.int32)
+        P = C.c_void_p
+        ptr = lambda a: None if a is None else a.ctypes.data_as(P)
+        self.check(self.lib.t4_add_query_pool_begin2(ix.h, n, ptr(buf), ptr(off), None, ptr(st), 0, ptr(fa), None, ptr(only), ptr(force), want_cands))
+        pc, pb, po, pe, pr = P(), P(), P(), P(), P()
+        self.check(self.lib.t4_add_query_pool_end(self.h, C.byref(pc), C.byref(pb), C.byref(po), C.byref(pe), C.byref(pr)))
+        cnt = np.ctypeslib.as_array(C.cast(pc, C.POINTER(C.c_int32)), (n,)).copy()
+        base = np.ctypeslib.as_array(C.cast(pb, C.POINTER(C.c_int32)), (n,)).copy()
+        ov = []
+        for i in range(n):
+            k = max(int(cnt[i]), 0)
+            ov.append(np.frombuffer((C.c_char * (40 * k)).from_address(po.value + 40 * int(base[i])), dtype=OV_DTYPE, count=k).copy() if k else None)
+        cp, cb, cc, s8, nn = P(), P(), P(), P(), C.c_int(0)
+        self.check(self.lib.t4_add_query_last_cands(self.h, C.byref(cp), C.byref(cb), C.byref(cc), C.byref(s8), C.byref(nn)))
+        stats = np.ctypeslib.as_array(C.cast(s8, C.POINTER(C.c_int32)), (n, 12)).copy()
+        ax, n4, sta = P(), P(), P()
+        self.check(self.lib.t4_add_query_last_aux(self.h, C.byref(ax), C.byref(n4), C.byref(sta), C.byref(nn)))
+        status = np.ctypeslib.as_array(C.cast(sta, C.POINTER(C.c_int32)), (n,)).copy()
+        return {"counts": cnt, "status": status, "stats": stats, "ov": ov}
+
+    def query_head(self, i):
+        """t4_add_query_head: (M, head bitmap as M 0/1 values, removeOnlyRepeats minus | plus << 1) of read i of the last AddRead
+        query call when the wide query served it and it met a list beyond 10000 postings, else None"""
+        m, bits, ror = C.c_int(0), C.c_void_p(), C.c_int(0)
+        got = self.lib.t4_add_query_head(self.h, i, C.byref(m), C.byref(bits), C.byref(ror))
+        if got != 1:
+            if got < 0:
+                self.check(got)
+            return None
+        words = np.ctypeslib.as_array(C.cast(bits, C.POINTER(C.c_uint32)), ((m.value + 31) // 32,)).copy() if m.value else np.zeros(0, dtype=np.uint32)
+        return m.value, words, ror.value
+
+    def arm_long_lists(self, arm, head_word, heads):
+        """t4_add_query_arm_long_lists: arms the restricted re-queries of the next add_query_whole(..., only_seq=...) call"""
+        a = np.asarray(arm, dtype=np.int32)
+        w = np.asarray(head_word, dtype=np.int32)
+        h = np.ascontiguousarray(heads, dtype=np.uint32)
+        P = C.c_void_p
+        self.check(self.lib.t4_add_query_arm_long_lists(self.h, len(a), a.ctypes.data_as(P), w.ctypes.data_as(P), h.ctypes.data_as(P) if len(h) else None, len(h)))
+
+    def last_long_lists(self):
+        """t4_add_query_last_long_lists: per read of the last call 0x100 | group info of the contig's minus group | plus group << 4
+        (armed restricted re-queries that were answered; 0 otherwise), None when the call was not armed"""
+        info, n = C.c_void_p(), C.c_int(0)
+        self.check(self.lib.t4_add_query_last_long_lists(self.h, C.byref(info), C.byref(n)))
+        if not info.value:
+            return None
+        return np.ctypeslib.as_array(C.cast(info, C.POINTER(C.c_int32)), (n.value,)).copy()
 
     def index(self, k, consider_barcode=False):
         return Index(self, k, consider_barcode)

@@ -71,8 +71,9 @@ struct AqCall {
   int n = 0, skipRepeats = 0, wpk = 0, wnm = 0, attempt = 0, nFirst = 0, nDirect = 0, threads = 512;
   unsigned char *tierHint = nullptr;
   std::vector<unsigned char> allGlobal;
-  size_t oPk, oNm, oLen, oBc, oSt, oLs, oVw, oFa, oOnly, oForce, oCs, oWide, oWideA, inBytes, pCb, pCc, pS8, pCnt, pSta, pNext, pNext2, pBase, pTick, pStab, pAux, pN4, pTail, pWctl, pWplan, pWstat, pWctlA, pWplanA, pWstatA, outBytes;
+  size_t oPk, oNm, oLen, oBc, oSt, oLs, oVw, oFa, oOnly, oForce, oArm, oHead, pRor, oCs, oWide, oWideA, inBytes, pCb, pCc, pS8, pCnt, pSta, pNext, pNext2, pBase, pTick, pStab, pAux, pN4, pTail, pWctl, pWplan, pWstat, pWctlA, pWplanA, pWstatA, outBytes;
   bool hasOnly = false, hasForce = false, wantCands = false;
+  bool hasArm = false;   // restricted re-queries of reads with long lists, armed by t4_add_query_arm_long_lists (T4CandArgs::rorArm)
   bool keepExtAux = false;   // t4_assign_wide: one word per pool record beside the public records (T4CandArgs::extAux)
   bool extendLater = false, wide = false, onlyRestricted = false;
   bool sweep2Done = false;     // the second sweep of the wide kernels (first passes of skipRepeats queries that found nothing) has been looked at
@@ -156,6 +157,9 @@ struct t4_ctx {
   T4Wide wide;               // device pointers + capacities (a copy travels in every call's input blob)
   bool wideInit = false;
   unsigned char *grpPoolHost = nullptr;   // pinned; T4Wide::grpPool is its device address
+  unsigned *headBitsHost = nullptr;       // pinned; T4Wide::headBits is its device address
+  std::vector<int32_t> armWords;          // t4_add_query_arm_long_lists: T4CandArgs::rorArm of the next call with restricted re-queries (2 per read)
+  std::vector<uint32_t> armHead;          // ... and the head bitmaps its second words point into
   int64_t wideReads = 0, wideParts = 0, wideRetries = 0, wideGroups = 0;
   int64_t aqDeferredReads = 0;   // reads whose ExtendOverlap calls the query kernel left to extendKernel (T4QueryArgs::extendLater)
   int64_t wideCalls = 0, wideCallsDeferred = 0, wideCallsDirect = 0;   // calls with the wide query on; those whose query kernel deferred a read; those with reads on the second stream
@@ -319,6 +323,10 @@ int ensureWide(t4_ctx *c, int reads, int parts, int groups) {
     if ((r = devAlloc(c, &w.uniqPref, 2 * (size_t)n * (w.pcap + 1)))) return r;
     if ((r = devAlloc(c, &w.sortTmp, 2 * (size_t)n * 2 * w.pcap))) return r;
     if ((r = devAlloc(c, &w.requeue, 2 * (size_t)n))) return r;
+    if (c->headBitsHost) (void)hipHostFree(c->headBitsHost);
+    c->headBitsHost = nullptr; w.headBits = nullptr;
+    HIPCHK(c, hipHostMalloc(&c->headBitsHost, sizeof(unsigned) * 2 * (size_t)n * ((w.pcap + 31) / 32), hipHostMallocMapped));
+    HIPCHK(c, hipHostGetDevicePointer((void **)&w.headBits, c->headBitsHost, 0));
     w.maxReads = n;
   }
   if (parts > w.maxPart) {
@@ -356,7 +364,7 @@ T4Wide wideHalf(const t4_ctx *c, int half) {
   T4Wide w = c->wide;
   if (!half) return w;
   const size_t R = (size_t)w.maxReads, P = (size_t)w.maxPart;
-  w.seed += R * T4_WIDE_SEEDS; w.bounds += R * (T4_WIDE_MAXP + 1); w.uniqPref += R * (w.pcap + 1); w.sortTmp += R * 2 * w.pcap; w.requeue += R;
+  w.seed += R * T4_WIDE_SEEDS; w.bounds += R * (T4_WIDE_MAXP + 1); w.uniqPref += R * (w.pcap + 1); w.sortTmp += R * 2 * w.pcap; w.requeue += R; w.headBits += R * ((w.pcap + 31) / 32);
   w.pCnt += P; w.pRead += P; w.pKeys += P * w.pcap; w.gSize += P * w.pcap; w.gInfo += P * w.pcap; w.gCount += P * 4; w.gOff += P * 2;
   w.pRec += P * w.maxOvPart * 10; w.pRecCnt += P; w.mKeys += P * w.maxOvPart; w.mOrd += P * w.maxOvPart;
   w.grpPool += w.grpCap;
@@ -434,6 +442,7 @@ void t4_destroy(t4_ctx *c) {
                   c->wide.pRecCnt, c->wide.uniqPref, c->wide.mKeys, c->wide.mOrd, c->wide.sortTmp, c->wide.requeue};
     for (void *p : wp) if (p) (void)hipFree(p);
     if (c->grpPoolHost) (void)hipHostFree(c->grpPoolHost);
+    if (c->headBitsHost) (void)hipHostFree(c->headBitsHost);
   }
   for (void *p : ptrs) if (p) (void)hipFree(p);
   for (int i = 0; i < 4; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -701,6 +710,7 @@ int commitWithPostings(t4_index *ix, std::vector<Rec> &recs) {
       f.pwOff = (int)pw.size();
       for (int i = 0; i < f.len; ++i) pw.push_back(t4PwByte(s.pw[4 * i], s.pw[4 * i + 1], s.pw[4 * i + 2], s.pw[4 * i + 3]));
       pw.push_back(t4PwByte(0, 0, 0, 0));
+      pw[(size_t)f.pwOff] |= T4_PW_MARK_BAD;   // (an image made here carries no posting marks: a restricted re-query reads the posting lists instead, t4_kernels.h expandHitsContig)
     }
   }
   int r;
@@ -1756,14 +1766,21 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   q.oBc = al8(q.oLen + sizeof(int) * (size_t)n); q.oSt = al8(q.oBc + sizeof(int) * (size_t)n); q.oLs = al8(q.oSt + sizeof(int) * (size_t)n);
   q.oVw = al8(q.oLs + sizeof(int) * (size_t)n); q.oFa = al8(q.oVw + sizeof(int) * (size_t)n); q.oOnly = al8(q.oFa + sizeof(double) * (size_t)n);
   q.oForce = al8(q.oOnly + sizeof(int) * (size_t)n);
-  q.oCs = al8(q.oForce + sizeof(int) * (size_t)n);
+  // (armed restricted re-queries of reads with long lists: two words per read and the head bitmaps, beside oOnly / oForce; nothing without them)
+  q.hasArm = false;
+  if (!c->armWords.empty()) {
+    if (!onlySeq || c->armWords.size() != 2 * (size_t)n) { c->armWords.clear(); c->armHead.clear(); return fail(c, T4_ERR_ARG, "t4_add_query_arm_long_lists armed %d reads; the call that follows has %d%s", (int)(c->armWords.size() / 2), n, onlySeq ? "" : " and no restricted re-query"); }
+    q.hasArm = true;
+  }
+  q.oArm = al8(q.oForce + sizeof(int) * (size_t)n); q.oHead = al8(q.oArm + (q.hasArm ? sizeof(int) * 2 * (size_t)n : 0));
+  q.oCs = al8(q.oHead + (q.hasArm ? sizeof(unsigned) * c->armHead.size() : 0));
   q.oWide = al8(q.oCs + sizeof(T4CandArgs)); q.hasOnly = onlySeq != nullptr; q.hasForce = forceMin != nullptr; q.wantCands = (wantCands & 1) != 0; q.keepExtAux = (wantCands & 2) != 0;
   q.oWideA = al8(q.oWide + sizeof(T4Wide)); q.inBytes = al8(q.oWideA + sizeof(T4Wide));
   q.pCnt = 0; q.pSta = al8(q.pCnt + sizeof(int) * (size_t)n); q.pNext = al8(q.pSta + sizeof(int) * (size_t)n);
   q.pNext2 = al8(q.pNext + sizeof(int) * (size_t)n); q.pBase = al8(q.pNext2 + sizeof(int) * (size_t)n);
   q.pTick = al8(q.pBase + sizeof(int) * (size_t)n); q.pStab = al8(q.pTick + sizeof(int) * (size_t)n); q.pAux = al8(q.pStab + sizeof(int) * (size_t)n);
   q.pN4 = al8(q.pAux + sizeof(int) * (size_t)n); q.pCb = al8(q.pN4 + sizeof(int) * (size_t)n); q.pCc = al8(q.pCb + sizeof(int) * (size_t)n);
-  q.pS8 = al8(q.pCc + sizeof(int) * (size_t)n); q.pTail = al8(q.pS8 + sizeof(int) * T4_QSTATS * (size_t)n);   // tail: overflow1 | overflow2 | hits (8 B) | pool cursor | dir overflow | cand cursor | cand overflow | reads deferred to extendKernel
+  q.pS8 = al8(q.pCc + sizeof(int) * (size_t)n); q.pRor = al8(q.pS8 + sizeof(int) * T4_QSTATS * (size_t)n); q.pTail = al8(q.pRor + (q.hasArm ? sizeof(int) * (size_t)n : 0));   // tail: overflow1 | overflow2 | hits (8 B) | pool cursor | dir overflow | cand cursor | cand overflow | reads deferred to extendKernel
   const size_t nW = (size_t)n * (skip_repeats ? 2 : 1);   // (a first pass that finds nothing leaves its slot and takes a new one in the second sweep)
   q.nWideSlots = (int)nW;
   q.pWctl = q.pTail + 48; q.pWplan = q.pWctl + 32; q.pWstat = al8(q.pWplan + sizeof(T4WidePlan) * nW);
@@ -1793,6 +1810,11 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   auto tp0 = tNow();
   unsigned char *h = c->aqInHost;
   memset(h, 0, q.inBytes);
+  if (q.hasArm) {   // (consumed: the arming holds for this call alone)
+    memcpy(h + q.oArm, c->armWords.data(), sizeof(int) * c->armWords.size());
+    if (!c->armHead.empty()) memcpy(h + q.oHead, c->armHead.data(), sizeof(unsigned) * c->armHead.size());
+    c->armWords.clear(); c->armHead.clear();
+  }
   unsigned *pk = (unsigned *)(h + q.oPk), *nm = (unsigned *)(h + q.oNm);
   int *len = (int *)(h + q.oLen), *bc = (int *)(h + q.oBc), *st = (int *)(h + q.oSt), *ls = (int *)(h + q.oLs), *vw = (int *)(h + q.oVw);
   double *fa = (double *)(h + q.oFa);
@@ -1912,6 +1934,7 @@ int aqLaunch(t4_ctx *c) {
     memset(&cs, 0, sizeof cs);
     cs.stats8 = (int *)(c->aqOut + q.pS8);
     if (q.hasForce) cs.forceMin = (const int *)(c->aqIn + q.oForce);
+    if (q.hasArm) { cs.rorArm = (const int *)(c->aqIn + q.oArm); cs.rorHead = (const unsigned *)(c->aqIn + q.oHead); cs.rorInfo = (int *)(c->aqOut + q.pRor); }
     if (q.keepExtAux) {   // (sized with the pool: a call repeated with a larger pool comes through here again)
       if (c->aqExtAuxCap < c->aqPoolCap) {
         c->aqExtAuxCap = 0;
@@ -2431,6 +2454,67 @@ int t4_add_query_groups(t4_ctx *c, int i, const t4_grp **groups, int *n, int *hu
     }
   }
   return 0;
+}
+
+// The head of read i of the last finished AddRead query call on this ctx, when the wide query served it and one of its lists holds
+// more than 10000 postings (`huge`): what the run test of SeqSet.hpp:931-947 reads of the read's hit array. Returns 1 with M, the
+// head as a bitmap of M bits (bit k of word k / 32: entry k has a list of at most 10000 postings; pinned memory the statistics
+// kernel wrote, valid until the next call) and removeOnlyRepeats of the minus strand | of the plus strand << 1; 0 for any other read
+// (nothing is kept for those). M is 0 when neither flag is set: no test reads the head then.
+int t4_add_query_head(t4_ctx *c, int i, int *m, const uint32_t **bits, int *ror) {
+  if (!c || !m || !bits || !ror) return T4_ERR_ARG;
+  const AqCall &q = c->aq;
+  if (!q.wide || !c->aqOutHost || !c->headBitsHost) return 0;
+  const unsigned char *o = c->aqOutHost;
+  for (int half = 0; half < 2; ++half) {
+    const int *ctl = (const int *)(o + (half ? q.pWctlA : q.pWctl));
+    const T4WidePlan *plan = (const T4WidePlan *)(o + (half ? q.pWplanA : q.pWplan));
+    const int *stat = (const int *)(o + (half ? q.pWstatA : q.pWstat));
+    const int nw = ctl[0] < q.nWideSlots ? ctl[0] : q.nWideSlots;
+    for (int w = 0; w < nw; ++w) {
+      if (plan[w].read != i) continue;
+      if (!plan[w].huge) return 0;
+      const int *st = stat + (size_t)w * T4_WIDE_STAT;
+      *m = st[WS_M];
+      *ror = (st[WS_ROR] ? 1 : 0) | (st[WS_ROR + 1] ? 2 : 0);
+      *bits = c->headBitsHost + ((half ? (size_t)c->wide.maxReads : 0) + (size_t)w) * ((c->wide.pcap + 31) / 32);
+      return 1;
+    }
+  }
+  return 0;
+}
+
+// Arms the restricted re-queries of the NEXT t4_add_query_pool_begin2 call on this ctx (which must have n reads and an only_seq)
+// with what the removeOnlyRepeats tests need of each read's last whole query: arm[i] = the flag of the minus strand | of the plus
+// strand << 1 | 4 | M << 3 (0: read i is not armed and takes the plain restricted path), head_word[i] = first word of its head
+// bitmap in `heads` (n_words words, copied). The arming is consumed by that call.
+int t4_add_query_arm_long_lists(t4_ctx *c, int n, const int32_t *arm, const int32_t *head_word, const uint32_t *heads, int n_words) {
+  if (!c || n < 0 || n_words < 0 || (n > 0 && (!arm || !head_word)) || (n_words > 0 && !heads)) return T4_ERR_ARG;
+  c->armWords.clear(); c->armHead.clear();
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    if (!arm[i]) continue;
+    const int m = arm[i] >> 3;
+    if (!(arm[i] & 4) || m < 0 || m > 8192 || head_word[i] < 0 || (int64_t)head_word[i] + (m + 31) / 32 > n_words)
+      return fail(c, T4_ERR_ARG, "t4_add_query_arm_long_lists: read %d: arm word %d, head word %d of %d", i, arm[i], head_word[i], n_words);
+    any = true;
+  }
+  if (!any) return T4_OK;
+  c->armWords.resize(2 * (size_t)n);
+  for (int i = 0; i < n; ++i) { c->armWords[2 * (size_t)i] = arm[i]; c->armWords[2 * (size_t)i + 1] = arm[i] ? head_word[i] : 0; }
+  c->armHead.assign(heads, heads + n_words);
+  return T4_OK;
+}
+
+// per read of the last finished AddRead query call on this ctx (n entries, valid until the next call), null when the call was not
+// armed: 0x100 | the group-info bits (t4_grp: bits 24-27 of cnt) of the one contig's minus group | of its plus group << 4 for an
+// armed restricted re-query that was answered, 0 otherwise
+int t4_add_query_last_long_lists(t4_ctx *c, const int32_t **info, int *n) {
+  if (!c || !info) return T4_ERR_ARG;
+  const AqCall &q = c->aq;
+  *info = (q.hasArm && c->aqOutHost) ? (const int32_t *)(c->aqOutHost + q.pRor) : nullptr;
+  if (n) *n = q.n;
+  return T4_OK;
 }
 
 // per read of the last finished AddRead query call on this ctx (n entries, valid until the next call): aux and n4 as T4QueryArgs

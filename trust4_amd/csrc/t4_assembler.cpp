@@ -613,6 +613,12 @@ struct t4_assembler : IndexListener {
     std::vector<uint8_t> devInfo;
     bool ror0[2] = {false, false}, rorOk = false;
     std::vector<uint32_t> editedKeys;
+    // ... and the head of the hit array as its last whole query left it (t4_add_query_head; kept under T4_FRAGILE_CHECKS only): the first
+    // headM entries in the reference's order as a bitmap, 1 = list of at most 10000 postings. A restricted re-query of such an entry is
+    // armed with it (t4_add_query_arm_long_lists) and applies the two removeOnlyRepeats tests to its one contig.
+    std::vector<uint32_t> headBits;
+    int headM = 0;
+    bool headOk = false;
     std::vector<Grp> dbgGroups;   // T4_VERIFY_WINDOW: what buildGroups derives for a read the wide query serves
     bool hostRecords = false;     // ... derived on the host (buildGroups: the emitted hits of a read of the LDS tier), not returned by the wide query
     bool expectWide = false;      // the launch expects the wide query to serve this read: no table derived beside the launch
@@ -756,6 +762,7 @@ struct t4_assembler : IndexListener {
   int64_t candRecords = 0, candMerges = 0, candFallbackUncut = 0, candFallbackStats = 0, candFallbackStrand = 0, candFallbackOther = 0, candRecut = 0, candSelfChecks = 0, candMergesBig = 0, candMergesStats = 0, candExactStats = 0, candRaised = 0;
   bool mergeRestricted(Cached &c, int pc, int k2, const t4_overlap *ov, const t4_overlap *ex, const int32_t *rets, const t4_cand *nc, int ncnt, const int32_t *s8);
   static void replayScan(const std::vector<t4_cand> &cands, const std::vector<Seq> &seqs, int len, int radius, double repeatSim, std::vector<unsigned char> &cut);
+  int64_t longListMerged = 0;   // restricted re-queries of entries with lists beyond 10000 postings that were merged
   int64_t whyNot[6] = {0, 0, 0, 0, 0, 0};   // entries that fell whole although one contig changed: lists beyond 10000 postings, overlaps on the other strand, more than 44 candidate overlaps, more than ~100 groups of four hits, no report from the query, other
   // (precondition of every restricted path: what the entry's result takes from one contig is independent of the other contigs. The
   // one step of GetOverlapsFromRead that pairs hits ACROSS sequences, the VJ-junction rescue of SeqSet.hpp:1570-1575, considers
@@ -764,7 +771,10 @@ struct t4_assembler : IndexListener {
   bool eligibleForRestricted(const Cached &e) {
     if (!e.valid || e.skip || e.barcode != -1) { ++whyNot[5]; return false; }
     if (!e.auxOk) { ++whyNot[4]; return false; }
-    if (e.fragile) { ++whyNot[0]; return false; }
+    // (a read with lists beyond 10000 postings: removeOnlyRepeats and the run test of SeqSet.hpp:931-947 look across its contigs. With
+    // T4_FRAGILE_CHECKS, the query's own records and the head of its hit array, the re-query applies both tests to its one contig and the
+    // entry is held to the same thresholds, flags, head and largest group when the records arrive: harvest)
+    if (e.fragile && !(knobs.fragileChecks && knobs.exactTolerance && e.rorOk && e.maskOk && !e.inexact && e.hasDev && e.candOk && e.headOk)) { ++whyNot[0]; return false; }
     if (e.nOther != 0) { ++whyNot[1]; return false; }
     if (candStore && e.candOk) return true;   // (the replay of the scan and the certificate of the group statistics decide when the records arrive)
     if (e.nAllBound > 44) { ++whyNot[2]; return false; }
@@ -776,7 +786,7 @@ struct t4_assembler : IndexListener {
   int emittedHits(Cached &e);
   int64_t headWholeWhy[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int64_t toleranceChecks = 0, toleranceCheckKills = 0, groupSelfChecks = 0, fragileChecks = 0;
-  bool exactStats(const Cached &c, int pc, const int32_t *pcSize, int T[2], int e4[2], int e5[2], int big[2], bool *ror = nullptr, int headLen = 0, bool *headTouched = nullptr);
+  bool exactStats(const Cached &c, int pc, const int32_t *pcSize, int T[2], int e4[2], int e5[2], int big[2], bool *ror = nullptr, int headLen = 0, bool *headTouched = nullptr, const int *pcInfo = nullptr);
   int64_t deltas = 0, deltaBytes = 0, rounds = 0, readsQueried = 0, invKey = 0, invCross = 0, invRegion = 0, invShift = 0, invContig = 0, invFragile = 0, tolerated = 0;
   double secDelta = 0, secGroups = 0, secEvents = 0, secRegister = 0, secPrefetch = 0, secAddTotal = 0;
 
@@ -917,6 +927,7 @@ struct t4_assembler : IndexListener {
     int polls = 0;
     std::vector<int> slots; std::vector<int64_t> uids; std::vector<unsigned char> hint;
     std::string bases; std::vector<int64_t> offs; std::vector<int32_t> bcs, sts, only, force; std::vector<double> fac;
+    std::vector<int32_t> arm, headWord; std::vector<uint32_t> heads;   // t4_add_query_arm_long_lists: restricted re-queries of entries with lists beyond 10000 postings
     int repetitive = 0;
   };
   std::vector<Lane> lanes;
@@ -2123,7 +2134,7 @@ void t4_assembler::processEvents() {
     for (int sl : checkSlots) {
       Cached &e = *pool[sl];
       e.checkPending = false;
-      if (!e.valid) { e.editedKeys.clear(); continue; }
+      if (!e.valid) { if (!(e.fragile && e.partial)) e.editedKeys.clear(); continue; }   // (an entry with long lists that waits for a restricted re-query: the edits are held against the head when its records arrive)
       int T[2], e4[2], e5[2], big[2];
       bool ror[2] = {false, false}, headTouched = false;
       ++toleranceChecks;
@@ -2165,7 +2176,7 @@ void t4_assembler::announceLive(int n, const char *const *reads, const int *stra
     c.inflight = false; c.killed = false; c.shifts.clear();
     c.ov.clear(); c.ext.clear(); c.extRet.clear();
     c.uid = nextUid++; c.tier = 0; c.hintPredicted = false; c.lastUs = 0; c.registered = false; c.lastKill = 0;
-    c.hasDev = false; c.hostRecords = false; c.expectWide = false; c.conservative = false; c.sawCommit = false; c.devGroups.clear(); c.dbgGroups.clear(); c.devInfo.clear(); c.rorOk = false; c.editedKeys.clear();
+    c.hasDev = false; c.hostRecords = false; c.expectWide = false; c.conservative = false; c.sawCommit = false; c.devGroups.clear(); c.dbgGroups.clear(); c.devInfo.clear(); c.rorOk = false; c.headOk = false; c.editedKeys.clear();
     c.partial = false; c.pendingContig = -1; c.merged = false; c.auxOk = false; c.restrictedCount = 0; c.kmerPos.clear();
     c.cands.clear(); c.candOk = false; c.exactKeys.clear(); c.morePending.clear(); c.inexact = false; c.repeatNear = false; c.checkPending = false; c.maskOk = false;
     order.push_back(sl);
@@ -2185,13 +2196,18 @@ int t4_assembler::launchOn(Lane &L, const std::vector<int> &todo, int repetitive
   ts.lap(TS_DELTA);
   wideQueries = knobs.wideQueries; wideHitLimit = knobs.wideHitLimit;   // what t4_add_query_pool_begin2 does with a heavy read under the testing aids of csrc/t4_api.hip
   // one item per whole query, one per contig a partial entry waits for (the items of an entry are adjacent)
-  L.slots.clear(); L.uids.clear(); L.hint.clear(); L.bcs.clear(); L.sts.clear(); L.fac.clear(); L.only.clear(); L.force.clear();
+  L.slots.clear(); L.uids.clear(); L.hint.clear(); L.bcs.clear(); L.sts.clear(); L.fac.clear(); L.only.clear(); L.force.clear(); L.arm.clear(); L.headWord.clear(); L.heads.clear();
   L.bases.clear(); L.offs.assign(1, 0); L.repetitive = repetitive;
-  bool anyOnly = false;
+  bool anyOnly = false, anyArmed = false;
   for (int i = 0; i < m; ++i) {
     Cached &c = *pool[todo[i]];
     const int nItems = c.partial ? 1 + (int)c.morePending.size() : 1;
+    // (an entry with lists beyond 10000 postings: its re-queries apply the removeOnlyRepeats tests with the flags and the head of its whole query)
+    const bool armed = c.partial && c.fragile && c.headOk;
+    const int headAt = (int)L.heads.size();
+    if (armed) { L.heads.insert(L.heads.end(), c.headBits.begin(), c.headBits.end()); anyArmed = true; }
     for (int t = 0; t < nItems; ++t) {
+      L.arm.push_back(armed ? ((c.ror0[0] ? 1 : 0) | (c.ror0[1] ? 2 : 0) | 4 | (c.headM << 3)) : 0); L.headWord.push_back(armed ? headAt : 0);
       L.slots.push_back(todo[i]); L.uids.push_back(c.uid); L.hint.push_back(c.tier);
       L.bases += c.read; L.offs.push_back((int64_t)L.bases.size()); L.bcs.push_back(c.barcode); L.sts.push_back(c.strand);
       L.fac.push_back((c.barcode == -1 && !repetitive) ? 1.0 : 2.0);   // ExtendOverlap's mismatch factor (SeqSet.hpp:3597-3598)
@@ -2201,7 +2217,7 @@ int t4_assembler::launchOn(Lane &L, const std::vector<int> &todo, int repetitive
     c.inflight = true; c.killed = false; c.shifts.clear();
     if (c.partial) { anyOnly = true; continue; }   // restricted re-query: the entry keeps what it holds of the other contigs
     c.statsStable = false;
-    c.hasDev = false; c.hostRecords = false; c.expectWide = false; c.conservative = false; c.sawCommit = false; c.devGroups.clear(); c.dbgGroups.clear(); c.devInfo.clear(); c.rorOk = false; c.editedKeys.clear();
+    c.hasDev = false; c.hostRecords = false; c.expectWide = false; c.conservative = false; c.sawCommit = false; c.devGroups.clear(); c.dbgGroups.clear(); c.devInfo.clear(); c.rorOk = false; c.headOk = false; c.editedKeys.clear();
     c.auxOk = false; c.merged = false; c.restrictedCount = 0;
     c.cands.clear(); c.candOk = false; c.exactKeys.clear();
   }
@@ -2215,7 +2231,8 @@ int t4_assembler::launchOn(Lane &L, const std::vector<int> &todo, int repetitive
   {
     auto tq0 = std::chrono::steady_clock::now();
     candStore = knobs.candStore;
-    rc = t4_add_query_pool_begin2(L.dev, mi, L.bases.data(), L.offs.data(), L.bcs.data(), L.sts.data(), repetitive, L.fac.data(), L.hint.data(), anyOnly ? L.only.data() : nullptr,
+    rc = anyArmed ? t4_add_query_arm_long_lists(L.ctx, mi, L.arm.data(), L.headWord.data(), L.heads.data(), (int)L.heads.size()) : T4_OK;
+    if (!rc) rc = t4_add_query_pool_begin2(L.dev, mi, L.bases.data(), L.offs.data(), L.bcs.data(), L.sts.data(), repetitive, L.fac.data(), L.hint.data(), anyOnly ? L.only.data() : nullptr,
                                   anyOnly ? L.force.data() : nullptr, candStore ? 1 : 0);
     secQuery += std::chrono::duration<double>(std::chrono::steady_clock::now() - tq0).count();
   }
@@ -2358,7 +2375,8 @@ void t4_assembler::replayScan(const std::vector<t4_cand> &cands, const std::vect
 // Out: novelMinHitRequired per strand (813-823), groups of >= 4 / >= 5 hits and the largest group (true sizes).
 // ror (optional, entries with lists beyond 10000 postings): removeOnlyRepeats per strand -- some group holds three hits of shorter lists in
 // its measured part (796-806). headTouched: one of c.editedKeys lies within the first headLen hits of the array in the reference's order.
-bool t4_assembler::exactStats(const Cached &c, int pc, const int32_t *pcSize, int T[2], int e4[2], int e5[2], int big[2], bool *ror, int headLen, bool *headTouched) {
+// pcInfo (with pc and ror): what the re-query reported of pc's two groups for that test, in place of the records' (stale) bits.
+bool t4_assembler::exactStats(const Cached &c, int pc, const int32_t *pcSize, int T[2], int e4[2], int e5[2], int big[2], bool *ror, int headLen, bool *headTouched, const int *pcInfo) {
   if (!c.hasDev || c.inexact) return false;
   if (ror) { if (c.devInfo.size() != c.devGroups.size()) return false; ror[0] = ror[1] = false; }
   if (headTouched) *headTouched = false;
@@ -2396,12 +2414,14 @@ bool t4_assembler::exactStats(const Cached &c, int pc, const int32_t *pcSize, in
     hitsBefore += n;
   };
   auto before = [](uint32_t a, uint32_t b) { return (a & 1u) != (b & 1u) ? (a & 1u) < (b & 1u) : a < b; };
+  const auto infoOfExtra = [&](uint32_t key) { return (ror && pcInfo && pc >= 0 && (key >> 1) == (uint32_t)pc) ? pcInfo[(int)(key & 1u)] : 0; };
   for (const Grp *g = d0; g < d1; ++g) {
     // (a group the host has added since holds fewer than three hits: no three of shorter lists, whatever they are)
-    while (xe < extra.size() && before(extra[xe].key, g->key)) { visit(extra[xe].key, extra[xe].cnt, 0); ++xe; }
-    visit(g->key, pc >= 0 && (g->key >> 1) == (uint32_t)pc ? pcSize[(int)(g->key & 1u)] : (int)g->cnt, ror ? (int)c.devInfo[(size_t)(g - d0)] : 0);
+    while (xe < extra.size() && before(extra[xe].key, g->key)) { visit(extra[xe].key, extra[xe].cnt, infoOfExtra(extra[xe].key)); ++xe; }
+    const bool isPc = pc >= 0 && (g->key >> 1) == (uint32_t)pc;
+    visit(g->key, isPc ? pcSize[(int)(g->key & 1u)] : (int)g->cnt, !ror ? 0 : (isPc && pcInfo) ? pcInfo[(int)(g->key & 1u)] : (int)c.devInfo[(size_t)(g - d0)]);
   }
-  while (xe < extra.size()) { visit(extra[xe].key, extra[xe].cnt, 0); ++xe; }
+  while (xe < extra.size()) { visit(extra[xe].key, extra[xe].cnt, infoOfExtra(extra[xe].key)); ++xe; }
   for (int t = 0; t < 2; ++t) {
     T[t] = 3;
     if (possible[t] > 100000) T[t] = (int)(longest[t] * 0.75);
@@ -2627,6 +2647,8 @@ int t4_assembler::harvest(Lane &L) {
   (void)t4_add_query_last_aux(L.ctx, &aux, &n4s, &qstatus, &nAux);
   const t4_cand *candPool = nullptr; const int32_t *candBase = nullptr, *candCnt = nullptr, *stats8 = nullptr; int nCand = 0;
   (void)t4_add_query_last_cands(L.ctx, &candPool, &candBase, &candCnt, &stats8, &nCand);
+  const int32_t *longInfo = nullptr; int nLong = 0;   // armed restricted re-queries: what they report of their contig's two groups for removeOnlyRepeats
+  (void)t4_add_query_last_long_lists(L.ctx, &longInfo, &nLong);
   // The dependency records of the reads the wide query served are the bulk of what a round hands back (thousands of 16-byte records
   // per read; 17 G of them over the first 2 M pairs of C3, where copying them was a third of the pass): when a round brings many,
   // the host threads copy them side by side before the entries are gone through one after the other.
@@ -2678,9 +2700,45 @@ int t4_assembler::harvest(Lane &L) {
         if (!c.isPending(pc)) continue;
         const int k2 = cnts[q] > 0 ? cnts[q] : 0;
         if (c.candOk) {   // the candidate store: swap the contig's candidates, repeat the scan, check the group statistics
-          const bool fits = !(qstatus && q < nAux && qstatus[q] == 5) && candPool && candCnt && q < nCand && candCnt[q] == k2;
+          bool fits = !(qstatus && q < nAux && qstatus[q] == 5) && candPool && candCnt && q < nCand && candCnt[q] == k2;
+          int pcInfo[2] = {0, 0};
+          if (fits && c.fragile) {
+            // An entry with lists beyond 10000 postings stands on more than its own contigs' records: the statistics loop over its groups
+            // as they are now, pc's at the sizes and with the hits of shorter lists this re-query reports, must give the thresholds and
+            // the removeOnlyRepeats flags the entry's candidates were made with; no edit since its whole query, pc's own included, may lie
+            // within the head of the hit array the run test reads; and the largest group -- the length of that head -- must be what it was.
+            const int32_t *s8q = stats8 + T4_QUERY_STATS * (size_t)q;
+            fits = c.headOk && longInfo && q < nLong && (longInfo[q] & 0x100) != 0;
+            if (fits) {
+              pcInfo[0] = longInfo[q] & 15; pcInfo[1] = (longInfo[q] >> 4) & 15;
+              const size_t nEdited = c.editedKeys.size();
+              c.editedKeys.push_back((uint32_t)pc * 2u); c.editedKeys.push_back((uint32_t)pc * 2u + 1u);
+              int T[2], e4[2], e5[2], big[2];
+              bool ror[2] = {false, false}, headTouched = false;
+              const int headLen = c.smhi[0] > c.smhi[1] ? c.smhi[0] : c.smhi[1];
+              fits = exactStats(c, pc, s8q + 4, T, e4, e5, big, ror, headLen, &headTouched, pcInfo) && T[0] == c.minT[0] && T[1] == c.minT[1] &&
+                     ror[0] == c.ror0[0] && ror[1] == c.ror0[1] && !headTouched && (big[0] > big[1] ? big[0] : big[1]) == headLen;
+              c.editedKeys.resize(nEdited);
+              // (a group the whole query's records do not hold has no place for its bits: it may stay while it cannot set a flag)
+              for (int t = 0; t < 2 && fits; ++t) {
+                const Grp *g = c.findGroup((uint32_t)pc * 2u + (uint32_t)t);
+                const bool inDev = g && g >= c.devGroups.data() && g < c.devGroups.data() + c.devGroups.size();
+                if (!inDev && s8q[4 + t] > 0 && (pcInfo[t] & 7) >= 3) fits = false;
+              }
+            }
+            ++fragileChecks;
+            if (!fits) ++invLongLists;
+          }
           if (fits && mergeRestricted(c, pc, k2, ov + bas[q], ex + bas[q], rets + bas[q], candPool + (k2 ? candBase[q] : 0), k2, stats8 + T4_QUERY_STATS * (size_t)q)) {
             ++c.restrictedCount; ++restrictedMerged;
+            if (c.fragile) {   // pc's bits as reported; the threshold of such an entry is never taken as certified (every edit is checked: processEvents)
+              for (int t = 0; t < 2; ++t) {
+                const Grp *g = c.findGroup((uint32_t)pc * 2u + (uint32_t)t);
+                if (g && g >= c.devGroups.data() && g < c.devGroups.data() + c.devGroups.size()) c.devInfo[(size_t)(g - c.devGroups.data())] = (uint8_t)pcInfo[t];
+              }
+              c.statsStable = false;
+              ++longListMerged;
+            }
           } else { fell = true; c.candOk = false; if (!fits) ++candFallbackOther; }
         } else {
           bool ok = !(qstatus && q < nAux && qstatus[q] == 5);
@@ -2708,7 +2766,7 @@ int t4_assembler::harvest(Lane &L) {
       ts.lap(TS_HARVEST_MERGE);
       if (fell) { c.partial = false; c.pendingContig = -1; c.morePending.clear(); c.lastKill = 7; ++restrictedFallbacks; continue; }   // neither valid nor partial: the whole query, next launch
       c.merged = true;
-      if (c.pendingContig < 0) { c.partial = false; c.valid = true; }   // (else a contig joined while the launch was out: the entry goes on waiting for that one)
+      if (c.pendingContig < 0) { c.partial = false; c.valid = true; c.editedKeys.clear(); }   // (else a contig joined while the launch was out: the entry goes on waiting for that one)
       continue;
     }
     c.tier = L.hint[i];
@@ -2756,7 +2814,7 @@ int t4_assembler::harvest(Lane &L) {
         static_assert(sizeof(t4_grp) == sizeof(Grp), "dependency record layout");
         if (!groupsCopied[(size_t)i]) c.devGroups.assign((const Grp *)dg, (const Grp *)dg + ng);
         c.devSplit = 0;
-        c.devInfo.clear(); c.rorOk = false;
+        c.devInfo.clear(); c.rorOk = false; c.headOk = false;
         if (huge) {   // (bits 24-27 of a record's count: T4_GRP_INFO_SHIFT in t4_wide.h)
           c.devInfo.resize(c.devGroups.size());
           for (size_t q = 0; q < c.devGroups.size(); ++q) { c.devInfo[q] = (uint8_t)((c.devGroups[q].cnt >> 24) & 15u); c.devGroups[q].cnt &= 0xFFFFFFu; }
@@ -2786,6 +2844,12 @@ int t4_assembler::harvest(Lane &L) {
         if (huge && c.candOk) {   // removeOnlyRepeats as this query found it, from its own records (exactStats repeats the loop the kernel ran)
           int T[2], e4[2], e5[2], big[2];
           c.rorOk = exactStats(c, -1, nullptr, T, e4, e5, big, c.ror0) && T[0] == c.minT[0] && T[1] == c.minT[1];
+          if (c.rorOk && knobs.fragileChecks) {   // the head of the hit array, for the restricted re-queries of this entry
+            int hm = 0, hror = 0; const uint32_t *hb = nullptr;
+            if (t4_add_query_head(L.ctx, i, &hm, &hb, &hror) == 1 && hror == ((c.ror0[0] ? 1 : 0) | (c.ror0[1] ? 2 : 0)) && (hror == 0 || hm == (big[0] > big[1] ? big[0] : big[1]))) {
+              c.headM = hm; c.headBits.assign(hb, hb + (hm + 31) / 32); c.headOk = true;
+            }
+          }
         }
         ++wideServed; wideGroupRecords += ng;
       } else if (c.expectWide) { buildGroups(c); ++wideMispredicted; }   // (the LDS tier served it after all)
@@ -3120,6 +3184,8 @@ int t4_assembler_live_counters(const t4_assembler *a, int64_t *out, int n) {
   if (n >= 23) t4_add_query_stats(a->ctx, out + 16);
   if (n >= 27) t4_add_query_wide_stats(a->ctx, out + 23);   // the wide query: reads it served, partitions, calls repeated with larger pools, dependency records
   if (n >= 28) out[27] = a->wideServed;   // window entries whose whole query the wide query served (all lanes)
+  if (n >= 29) out[28] = a->longListMerged;   // restricted re-queries of entries with lists beyond 10000 postings that were merged
+  if (n >= 30) out[29] = a->whyNot[0];        // entries that fell whole to a change of one contig because they hold such lists
   if (getenv("T4_VERIFY_WINDOW")) fprintf(stderr, "T4_VERIFY_WINDOW: the host's replay of the emitted hits equals the wide query's dependency records for all %lld reads it was held against\n", (long long)a->groupSelfChecks);
   if (getenv("T4_VERIFY_WINDOW")) fprintf(stderr, "T4_VERIFY_WINDOW: %lld served window entries queried again at serve time, all equal to their cached results (%lld of them put together from restricted re-queries)\n", (long long)a->verified, (long long)a->verifiedMerged);
   if (getenv("T4_TIMING")) {
@@ -3140,6 +3206,7 @@ int t4_assembler_live_counters(const t4_assembler *a, int64_t *out, int n) {
             (long long)a->tolerated, (long long)a->toleratedStable, (long long)a->invFragile, (long long)a->invLongLists);
     fprintf(stderr, "timing: restricted re-queries: %lld entries kept their other contigs when one contig changed, %lld merged, %lld fell back to the whole query, %lld in flight met another change of their contig\n",
             (long long)a->restrictedMarks, (long long)a->restrictedMerged, (long long)a->restrictedFallbacks, (long long)a->restrictedStale);
+    fprintf(stderr, "timing: entries with lists beyond 10000 postings: %lld restricted re-queries merged, %lld fell whole when one contig changed\n", (long long)a->longListMerged, (long long)a->whyNot[0]);
     fprintf(stderr, "timing: entries that fell whole when one contig changed: %lld with lists beyond 10000 postings, %lld with overlaps on the other strand, %lld with more than 44 candidate overlaps, %lld with ~100 groups of four hits, %lld without the query's report, %lld other\n",
             (long long)a->whyNot[0], (long long)a->whyNot[1], (long long)a->whyNot[2], (long long)a->whyNot[3], (long long)a->whyNot[4], (long long)a->whyNot[5]);
     fprintf(stderr, "timing: candidate store: %lld candidate records kept with whole queries, %lld restricted re-queries merged through the replay of the scan (%lld with more than 50 candidates, %lld with more than 100 groups of four hits on a strand, %lld cut a candidate of another contig), fell back to the whole query: %lld a cut candidate of another contig passes now, %lld the group statistics could move the threshold, %lld an overlap on the other strand, %lld other; %lld whole queries checked against the host's scan; %lld thresholds settled by repeating the statistics loop over the entry's groups, %lld raised thresholds served by dropping the candidates of shorter runs\n",

@@ -125,6 +125,7 @@ struct T4Wide {
   T4Grp *grpPool;            // pinned host memory (device pointer): dependency sets of the wide reads
   int grpCap;
   unsigned long long *sortTmp;  // [maxReads][2 * pcap] scratch of the statistics kernel (huge reads)
+  unsigned *headBits;        // pinned host memory (device pointer), [maxReads][(pcap + 31) / 32]: uniqPref's head as a bitmap (bit k = entry k has a list of at most 10000 postings), WS_M bits of it written -- what a later restricted re-query of the read is armed with
 };
 
 struct T4Work {              // per-launch work description
@@ -188,6 +189,15 @@ struct T4CandArgs {
   const int *forceMin;       // nullable
   int *extAux;               // nullable, one word per pool record: what ExtendOverlap's own record holds and the public one cannot carry -- 0 when the
                              // extension failed the similarity cut, else the denominator of its similarity (assignPickKernel reads it)
+  // nullable -- restricted re-queries of reads with lists beyond 10000 postings (t4_kernels.h restrictedRepeatTests). rorArm[2 r]:
+  // removeOnlyRepeats of the minus strand | of the plus strand << 1 | 4 (armed) | M << 3, all as the read's last whole query had them
+  // (0: read r is not armed and takes the plain restricted path); rorArm[2 r + 1]: first word of the read's head bitmap in rorHead
+  // (M bits, bit k = entry k of the head of its hit array in the reference's order has a list of at most 10000 postings).
+  // rorInfo[r] (out): 0x100 | the 4 group-info bits of the contig's minus group | of its plus group << 4, in the format of
+  // T4Wide::gInfo; 0 for a read that was not armed
+  const int *rorArm;
+  const unsigned *rorHead;
+  int *rorInfo;
 };
 // Bits 5-6 of a contig's predicate byte at offset o: the number of postings (contig, o) the index holds (0-3); bit 7 of the byte at
 // offset 0: the marks of this contig are not to be trusted (an offset with more than three postings). Written by the ordered

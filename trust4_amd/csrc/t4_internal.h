@@ -69,6 +69,11 @@ int t4_add_query_pool(t4_index *ix, int n, const char *bases, const int64_t *off
 // only_seq (nullable): only_seq[i] >= 0 asks for the overlaps of read i with that one contig alone -- all of them, both strands,
 // scored and extended, none of the steps that look across contigs applied (the restricted re-query of a window entry). It reads the
 // contig's postings off the posting marks of the image's predicate bytes (t4_device.h T4_PW_MARK_*, written by t4_assembler::makeDelta).
+// A read that meets a posting list beyond 10000 entries is answered like any other unless it was armed (t4_add_query_arm_long_lists,
+// below): then the two removeOnlyRepeats tests of GetOverlapsFromHits (SeqSet.hpp:871-887, 931-947) are applied to the contig's two
+// groups from the flags and the head of the read's last whole query (t4_add_query_head) and the list sizes of this call's own seed
+// stage, a run that ends beyond the head is refused (status 5: ask for the whole query), and the call reports what the statistics
+// loop reads of the contig's two groups for removeOnlyRepeats (t4_add_query_last_long_lists).
 // The candidate store: with want_cands the call also returns, per read, EVERY scored overlap of the pass on the strand of
 // the best one as it stands before the similarity cut (a restricted re-query: every overlap with its one contig) in the order of the
 // scan of SeqSet.hpp:1673-2094 -- pre-score key, scored fields, whether the pre-filters of 1705-1794 cut it -- and eight statistics
@@ -96,6 +101,17 @@ typedef struct { uint32_t key, cnt; int32_t lo, hi; } t4_grp;   // key = contig 
 // (records of a read with lists beyond 10000 postings -- `huge` -- carry in bits 24-27 of cnt what SeqSet.hpp:796-806 reads of the group:
 // bits 24-26 its hits of lists of at most 10000 postings, capped at 4; bit 27 whether its hit lowest on the read is one)
 int t4_add_query_groups(t4_ctx *ctx, int i, const t4_grp **groups, int *n, int *huge, int *n4);
+// the head of a `huge` read the wide query served: 1 with M, the first M entries of the read's hit array in the reference's order
+// (strand, contig, read offset) as a bitmap (1 = list of at most 10000 postings; pinned memory, valid until the next call) and
+// removeOnlyRepeats (minus | plus << 1); 0 for every other read -- nothing is kept for those
+int t4_add_query_head(t4_ctx *ctx, int i, int *m, const uint32_t **bits, int *ror);
+// arms the restricted re-queries of the NEXT t4_add_query_pool_begin2 call on the ctx (n reads, with only_seq): arm[i] = ror minus |
+// ror plus << 1 | 4 | M << 3 as t4_add_query_head gave them (0: not armed -- the plain restricted path), head_word[i] = first word
+// of the read's bitmap in heads[0, n_words) (copied)
+int t4_add_query_arm_long_lists(t4_ctx *ctx, int n, const int32_t *arm, const int32_t *head_word, const uint32_t *heads, int n_words);
+// per read of the last call, null when it was not armed: 0x100 | bits 24-27 of t4_grp::cnt as the one contig's minus group would
+// carry them | the plus group's << 4 (armed re-queries that were answered; 0 otherwise)
+int t4_add_query_last_long_lists(t4_ctx *ctx, const int32_t **info, int *n);
 int t4_add_query_wide_stats(t4_ctx *ctx, int64_t *out4);
 int t4_add_query_defer_stats(t4_ctx *ctx, int64_t *out1);
 int t4_add_query_last_call(t4_ctx *ctx, double *kernel_ms, const int32_t **ticks10ns, int *n);   // development aid (T4_ROUND_LOG)

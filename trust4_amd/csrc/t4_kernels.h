@@ -757,17 +757,24 @@ struct WaveState { // wave-uniform scalars kept in LDS
   int nvN4[2], nvN5[2], nvSmax[2];   // groups of at least 4 / 5 hits and the largest group, TRUE sizes (the statistics measure a group one short or in full)
   int statsStable;                   // no pass of this read so far whose novelMinHitRequired could move (see overlapsFromKeys)
   int hullLo[2], hullHi[2];          // restricted re-query: per strand, hull of the read's projections along the diagonals that hold three or more hits with the contig (lo > hi: none)
-  int spare;                         // unused: keeps the struct at 480 bytes, and with it where the kernels' other LDS arrays land (one int less cost the annotation kernel 3 %)
+  int rorArm;                        // restricted re-query of a read with lists beyond 10000 postings (restrictedRepeatTests): in, T4CandArgs::rorArm's first word (0: not armed); out, 0x100 | the contig's group info
   int forceMin[2];                   // restricted re-query: novelMinHitRequired per strand as the entry's whole query had it (0: three hits), T4QueryArgs::forceMin
   int vjRescue;                      // the pass ended in the VJ-junction rescue (GetVJOverlapsFromHits looks ACROSS sequences: such a result is not the sum of per-contig parts)
   int nAll, nOther, strand0;          // GetOverlapsFromRead: overlaps on the strand of the best one (before the similarity cut), on the other strand, that strand
+  union {                    // (the struct stays at 480 bytes, and with it where the kernels' other LDS arrays land: one int less cost the annotation kernel 3 %)
+    unsigned hhBest[2];      // HasHitInSet: per strand, (distinct read offsets << 16) | (0xFFFF - bucket rank) of the best bucket
+    const unsigned *rorHead; // AddRead query, with rorArm: the head bitmap of the read (global memory)
+  };
   int wideWant;                      // mode 4, nonzero: a pass that emits more hits than this (or outgrows the global-scratch tier) is handed to the wide query (t4_wide.h)
-  unsigned hhBest[2];        // HasHitInSet: per strand, (distinct read offsets << 16) | (0xFFFF - bucket rank) of the best bucket
   long long phaseT0; int curPhase, phaseBase;
 #ifdef T4_PHASE_TIMING
   unsigned phaseLocal[T4_NPHASE];
 #endif
 };
+
+#ifndef T4_PHASE_TIMING
+static_assert(sizeof(WaveState) == 480, "WaveState: its size decides where the kernels' other LDS arrays land");
+#endif
 
 // Build segment chars (forward + reverse complement of the segment) from the packed read.
 __device__ void loadSegment(const T4BatchView &bv, long long r, int segStart, int segLen, WaveMem &wm) {
@@ -2386,6 +2393,81 @@ __device__ int selectVJPair(const T4IndexView &ix, WaveMem &wm, int n) {
   return 2;
 }
 
+// The two removeOnlyRepeats tests of GetOverlapsFromHits (SeqSet.hpp:871-887, 931-947) for the ONE contig of a restricted re-query
+// whose read meets posting lists beyond 10000 entries (WaveState::rorArm, armed by the caller from the read's last whole query:
+// the flag per strand, and the head of the read's hit array in the reference's order as a bitmap, 1 = list of at most 10000
+// postings, M bits -- what wideStatsKernel leaves in T4Wide::uniqPref). The list size of a hit is the seed stage's: posPref.
+// keys[0, Hv): the contig's hits in key order, the nMinus hits of the minus strand first. With the flag of its strand set, a
+// group without a hit of a shorter list goes, and so does a qualifying run [rs, re) (relative to its group -- the reference
+// indexes the WHOLE hit array with it, a quirk: t4_wide.h) whose head entries are all of long lists; the hits of what goes are
+// taken out of the key array, so overlapsFromKeys never sees them. A qualifying run that ends beyond the head is not guessed:
+// -2, the caller asks for the whole query. Returns the hits that stay; leaves in ws->rorArm 0x100 | what SeqSet.hpp:796-806
+// reads of the minus group | of the plus group << 4 (hits of shorter lists capped at 4; 8: the hit lowest on the read is one).
+// Out of line: the AddRead kernel's common path pays one wave-uniform test for it.
+__device__ T4_NI int restrictedRepeatTests(const T4IndexView &ix, WaveMem &wm, WaveState *ws, int nk, int Hv, int nMinus, int hitLenRequired, const unsigned *posPref) {
+  const int lane = tid(), NT = nthr(), K = ix.k;
+  const int arm = ws->rorArm, M = arm >> 3;
+  const unsigned *head = ws->rorHead;
+  int *acc = ws->red + 8;   // [0..1] hits of shorter lists per group, [2..3] (read offset << 1 | its list is long) of the group's hit lowest on the read, [4] a run beyond the head
+  if (lane < 5) acc[lane] = (lane == 2 || lane == 3) ? 0x7FFFFFFF : 0;
+  __syncthreads();
+  if (Hv > 64 * NT) return -2;   // (the verdicts of a lane's hits ride in one 64-bit mask)
+  for (int i = lane; i < Hv; i += NT) {
+    const unsigned long long kt = wm.keys[i];
+    const int g = KEY_PLUS(kt), a = KEY_C(kt) - T4_C_BIAS + KEY_B(kt), q = g ? a : nk + a;
+    const bool small = posPref[q + 1] - posPref[q] <= 10000u;
+    if (small) atomicAdd(&acc[g], 1);
+    atomicMin(&acc[2 + g], (a << 1) | (small ? 0 : 1));
+  }
+  __syncthreads();
+  unsigned long long drop = 0;
+  int nDrop = 0;
+  for (int i = lane, t = 0; i < Hv; i += NT, ++t) {
+    const unsigned long long kt = wm.keys[i];
+    const int g = KEY_PLUS(kt);
+    if (!((arm >> g) & 1)) continue;
+    bool gone = acc[g] == 0;   // the group test
+    if (!gone) {
+      const unsigned long long dg = kt >> T4_B_BITS;   // (strand, contig, diagonal): a run of a contig set is a stretch of one diagonal
+      const int g0 = g ? nMinus : 0;
+      int s = i, e = i + 1;
+      while (s > 0 && (wm.keys[s - 1] >> T4_B_BITS) == dg) --s;
+      while (e < Hv && (wm.keys[e] >> T4_B_BITS) == dg) ++e;
+      const int minHit = ws->forceMin[g] > 0 ? ws->forceMin[g] : 3;
+      if (e - s >= minHit && (e - s) * K >= hitLenRequired) {
+        const int rs = s - g0, re = e - g0;
+        if (re > M) acc[4] = 1;
+        else {
+          bool uniq = false;
+          for (int w = rs >> 5; w <= ((re - 1) >> 5) && !uniq; ++w) {
+            unsigned v = head[w];
+            if (w == (rs >> 5)) v &= ~0u << (rs & 31);
+            if (w == ((re - 1) >> 5) && (re & 31)) v &= ~0u >> (32 - (re & 31));
+            uniq = v != 0u;
+          }
+          gone = !uniq;
+        }
+      }
+    }
+    if (gone) { drop |= 1ull << t; ++nDrop; }
+  }
+  nDrop = blockSum(nDrop, ws->red);   // (its barriers stand between the reads of the keys above and the writes below)
+  if (lane == 0) {
+    int info = 0x100;
+    for (int g = 0; g < 2; ++g) info |= ((acc[g] > 4 ? 4 : acc[g]) | ((acc[2 + g] != 0x7FFFFFFF && !(acc[2 + g] & 1)) ? 8 : 0)) << (4 * g);
+    ws->rorArm = info;
+  }
+  const int beyond = acc[4];
+  __syncthreads();
+  if (beyond) return -2;
+  if (nDrop == 0) return Hv;
+  for (int i = lane, t = 0; i < Hv; i += NT, ++t) if ((drop >> t) & 1ull) wm.keys[i] = ~0ull;   // behind every hit in key order
+  __syncthreads();
+  if (wm.ldsArrays) bitonicSortRegLds(wm.keys, Hv); else bitonicSort(wm.keys, Hv);
+  __syncthreads();
+  return Hv - nDrop;
+}
+
 // One GetHitsFromRead + GetOverlapsFromHits pass over the current segment. Returns H (hit records
 // emitted by the seed stage) or -1 on capacity overflow. Overlaps are left in wm.ov / ws->ovCount.
 template <bool NOVEL>   // NOVEL: the kernel variants that meet contig sets (repeat-skip rule live); the reference-set variants keep their register budget
@@ -2427,7 +2509,12 @@ __device__ int seedChainPass(const T4IndexView &ix, WaveMem &wm, WaveState *ws, 
       }
     }
     __syncthreads();
-    overlapsFromKeys(ix, wm, ws, Hv, hitLenRequired, 0);   // (filter 0: the thresholds are the caller's -- ws->forceMin, else three hits: it has made sure the group statistics leave them there)
+    int Hc = Hv;   // the hits that go on to the chains
+    if (ws->rorArm) {   // (wave-uniform) a read with lists beyond 10000 postings: the removeOnlyRepeats tests, armed by the caller
+      Hc = restrictedRepeatTests(ix, wm, ws, nk, Hv, Hv - nPlus, hitLenRequired, posPref);
+      if (Hc < 0) return -1;
+    }
+    overlapsFromKeys(ix, wm, ws, Hc, hitLenRequired, 0);   // (filter 0: the thresholds are the caller's -- ws->forceMin, else three hits: it has made sure the group statistics leave them there)
     if (lane == 0) {
       const int g[2] = {Hv - nPlus, nPlus};
       for (int t = 0; t < 2; ++t) { ws->nvN4[t] = g[t] >= 4 ? 1 : 0; ws->nvN5[t] = g[t] >= 5 ? 1 : 0; ws->nvSmax[t] = g[t]; }
@@ -3608,10 +3695,11 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
     const int onlySeq = qa.onlySeq ? qa.onlySeq[r] : -1;
     // (either pass of a skipRepeats query, barcoded reads too; an index keyed by barcode keeps its barcoded reads on this workgroup)
     const bool wide = onlySeq < 0 && wk.wide != nullptr && (barcode == -1 || !ix.considerBarcode) && ix.hasNovel == 2 && !qa.views && qa.extendLater > 0;
-    if (lane == 0) ws->wideWant = wide ? (wk.wide->minHits > 0 ? wk.wide->minHits : 1) : 0;
+    if (lane == 0) { ws->wideWant = wide ? (wk.wide->minHits > 0 ? wk.wide->minHits : 1) : 0; ws->rorArm = 0; }
     if (lane == 0 && qa.cs) {
       const T4CandArgs *cs = qa.cs;
       if (onlySeq >= 0 && cs->forceMin) { const int f = cs->forceMin[r]; ws->forceMin[0] = f & 0xFFFF; ws->forceMin[1] = (f >> 16) & 0xFFFF; }
+      if (onlySeq >= 0 && cs->rorArm && cs->rorArm[2 * r]) { ws->rorArm = cs->rorArm[2 * r]; ws->rorHead = cs->rorHead + cs->rorArm[2 * r + 1]; }
       if (cs->candCnt) cs->candCnt[r] = 0;
     }
     loadSegment(bv, r, 0, len, wm);
@@ -3637,7 +3725,7 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
     if (qa.cs && lane < 2) {
       int *s8 = qa.cs->stats8 + T4_QSTATS * r;
       s8[lane] = ws->nvN4[lane]; s8[2 + lane] = ws->nvN5[lane]; s8[4 + lane] = ws->nvSmax[lane]; s8[6 + lane] = ws->novelMin[lane];
-      if (onlySeq >= 0) { s8[8 + lane] = ws->hullLo[lane]; s8[10 + lane] = ws->hullHi[lane]; }
+      if (onlySeq >= 0) { s8[8 + lane] = ws->hullLo[lane]; s8[10 + lane] = ws->hullHi[lane]; if (lane == 0 && qa.cs->rorInfo) qa.cs->rorInfo[r] = ws->rorArm; }
     }
     if (qa.cs && qa.cs->candOut && ret >= 0) emitCands(qa.cs, wm, ws, r, onlySeq >= 0 ? ws->ovCount : ws->nAll, onlySeq >= 0);
     if (lane == 0) {   // room for this read's records in the result pool

@@ -474,6 +474,13 @@ __global__ __launch_bounds__(512) void wideStatsKernel(T4IndexView ix, T4Wide wd
     }
     if (lane == 0) { up[0] = 0; st[WS_M] = lim; }
     __syncthreads();
+    // the same head as a bitmap in host memory (t4_add_query_head): lim <= pcap bits
+    unsigned *hb = wd.headBits + (size_t)w * ((wd.pcap + 31) / 32);
+    for (int j = lane; j < (lim + 31) / 32; j += NT) {
+      unsigned v = 0;
+      for (int b = 0; b < 32 && j * 32 + b < lim; ++b) v |= (unsigned)(up[j * 32 + b + 1] - up[j * 32 + b]) << b;
+      hb[j] = v;
+    }
   }
 }
 

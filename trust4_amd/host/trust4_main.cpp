@@ -1962,8 +1962,8 @@ int main(int argc, char *argv[]) {
   t4_assembler_counters(seqSet, &q, &rf, &wh);
   double sr = 0, sq = 0;
   t4_assembler_timers(seqSet, &sr, &sq);
-  int64_t lc[27] = {0};
-  t4_assembler_live_counters(seqSet, lc, 27);
+  int64_t lc[30] = {0};
+  t4_assembler_live_counters(seqSet, lc, 30);
   mark("outputs_written");
   if (const char *sj = getenv("T4_STATS_JSON")) {
     FILE *fp = fopen(sj, "w");
@@ -1973,9 +1973,10 @@ int main(int argc, char *argv[]) {
       fprintf(fp, "}, \"rough_annotation\": {\"reads\": %lld, \"hits\": %lld, \"kernel_ms\": %.3f}, ", annotReads, annotHits, annotKernelMs);
       fprintf(fp, "\"add_query\": {\"rounds\": %lld, \"reads_queried\": %lld, \"reads_served\": %lld, \"kernel_ms\": %.3f, \"hits\": %lld, \"records\": %lld, "
                   "\"global_tier_launches\": %lld, \"global_tier_reads\": %lld, \"deltas\": %lld, \"delta_bytes\": %lld, \"invalidations\": %lld, \"host_wait_for_queries_s\": %.3f, "
-                  "\"wide\": {\"reads\": %lld, \"partitions\": %lld, \"calls_repeated\": %lld, \"dependency_records\": %lld}}, ",
+                  "\"wide\": {\"reads\": %lld, \"partitions\": %lld, \"calls_repeated\": %lld, \"dependency_records\": %lld}, "
+                  "\"long_lists\": {\"restricted_merged\": %lld, \"fell_whole\": %lld}}, ",
               (long long)lc[0], (long long)lc[1], (long long)wh, lc[21] / 1e3, (long long)lc[22], (long long)lc[20], (long long)lc[18], (long long)lc[19], (long long)lc[2],
-              (long long)lc[3], (long long)lc[4], lc[15] / 1e6, (long long)lc[23], (long long)lc[24], (long long)lc[25], (long long)lc[26]);
+              (long long)lc[3], (long long)lc[4], lc[15] / 1e6, (long long)lc[23], (long long)lc[24], (long long)lc[25], (long long)lc[26], (long long)lc[28], (long long)lc[29]);
       double cs[10] = {0};
       t4_assembler_chain_stats(seqSet, cs, 10);
       fprintf(fp, "\"chain\": {\"rounds\": %.0f, \"restricted_only_rounds\": %.0f, \"round_kernel_ms_p05\": %.4f, \"round_kernel_ms_p50\": %.4f, \"round_wall_ms_p05\": %.4f, \"round_wall_ms_p50\": %.4f, "
