@@ -61,6 +61,38 @@ struct HostSeq {
 
 }  // namespace
 
+struct t4_ctx;
+// A field of one of the call's two blobs: `count` elements of T, declared once in AqInput / AqHeader. The input blob is packed in
+// pinned staging memory and copied to the device by aqPrologueKernel; the header blob is written on the device and copied into
+// pinned host memory by aqEpilogueKernel.
+template <class T> struct AqField {
+  size_t off = 0;
+  bool header = false;
+  T *stage(const t4_ctx *c) const;        // input blob: the host's staging copy
+  T *dev(const t4_ctx *c) const;          // either blob: the device copy
+  const T *host(const t4_ctx *c) const;   // header blob: the pinned copy on the host
+};
+struct AqBlob {   // fields are appended in the order of the blob, each at the next multiple of 8 bytes
+  bool header = false;
+  size_t bytes = 0;
+  template <class T> void add(AqField<T> &f, size_t count) { f.off = bytes; f.header = header; bytes = (bytes + sizeof(T) * count + 7) & ~(size_t)7; }
+};
+struct AqInput : AqBlob {
+  AqField<unsigned> pk, nm;
+  AqField<int> len, barcode, strand, list /* the work lists: first launch, then second stream */, viewOf;
+  AqField<double> factor;
+  AqField<int> onlySeq, forceMin;
+  AqField<int> arm; AqField<unsigned> head;   // armed restricted re-queries (hasArm): T4CandArgs::rorArm, rorHead; empty otherwise
+  AqField<T4CandArgs> cs;
+  AqField<T4Wide> wide[2];   // the two halves of the wide query (wideHalf)
+};
+struct AqHeader : AqBlob {
+  AqField<int> counts, status, next, next2, outBase, ticks, stable, aux, n4, candBase, candCnt, stats8;
+  AqField<int> rorInfo;      // hasArm: T4CandArgs::rorInfo; empty otherwise
+  AqField<T4AqTail> tail;
+  struct { AqField<int> ctl; AqField<T4WidePlan> plan; AqField<int> stat; } wide[2];   // per half: T4Wide::ctl, plan, stat (nWideSlots read slots)
+};
+
 // The call is split in two so that a caller can keep the host busy while the kernels run (t4_assembler commits reads whose cached
 // queries still stand): aqBegin packs the input and enqueues copies + kernels + the header copy on the ctx's stream; aqEnd waits
 // for them, runs whatever overflow launch is still needed (rare paths, synchronous) and hands out the result. One call in flight
@@ -71,7 +103,7 @@ struct AqCall {
   int n = 0, skipRepeats = 0, wpk = 0, wnm = 0, attempt = 0, nFirst = 0, nDirect = 0, threads = 512;
   unsigned char *tierHint = nullptr;
   std::vector<unsigned char> allGlobal;
-  size_t oPk, oNm, oLen, oBc, oSt, oLs, oVw, oFa, oOnly, oForce, oArm, oHead, pRor, oCs, oWide, oWideA, inBytes, pCb, pCc, pS8, pCnt, pSta, pNext, pNext2, pBase, pTick, pStab, pAux, pN4, pTail, pWctl, pWplan, pWstat, pWctlA, pWplanA, pWstatA, outBytes;
+  AqInput in; AqHeader hdr;
   bool hasOnly = false, hasForce = false, wantCands = false;
   bool hasArm = false;   // restricted re-queries of reads with long lists, armed by t4_add_query_arm_long_lists (T4CandArgs::rorArm)
   bool keepExtAux = false;   // t4_assign_wide: one word per pool record beside the public records (T4CandArgs::extAux)
@@ -169,6 +201,9 @@ struct t4_ctx {
   double aqKernelMs = 0;    // HIP-event time of the query kernels of all AddRead query calls (per call: first launch .. last kernel)
   int64_t aqHits = 0;       // _hit records their seed stages emitted (H of SURVEY 8d)
 };
+template <class T> T *AqField<T>::stage(const t4_ctx *c) const { return (T *)(c->aqInHost + off); }
+template <class T> T *AqField<T>::dev(const t4_ctx *c) const { return (T *)((header ? c->aqOut : c->aqIn) + off); }
+template <class T> const T *AqField<T>::host(const t4_ctx *c) const { return (const T *)(c->aqOutHost + off); }
 
 struct t4_index {
   t4_ctx *ctx;
@@ -302,6 +337,15 @@ int ensurePerCall(t4_ctx *c, long long n) {
 // pools of the wide query (t4_wide.h): room for `reads` deferred reads, `parts` partitions of `pcap` keys and `groups` dependency
 // records per call; existing contents are never needed across calls, so growing reallocates
 int wideEnv(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+// The device pools with their elements per read slot / per partition: what ensureWide allocates and what wideHalf steps over.
+template <class F> void widePoolsPerRead(T4Wide &w, F f) {
+  f(w.seed, T4_WIDE_SEEDS); f(w.bounds, T4_WIDE_MAXP + 1); f(w.uniqPref, w.pcap + 1); f(w.sortTmp, 2 * (size_t)w.pcap); f(w.requeue, 1);
+}
+template <class F> void widePoolsPerPart(T4Wide &w, F f) {
+  f(w.pCnt, 1); f(w.pRead, 1); f(w.pKeys, w.pcap); f(w.gSize, w.pcap); f(w.gInfo, w.pcap); f(w.gCount, 4); f(w.gOff, 2);
+  f(w.pRec, (size_t)w.maxOvPart * 10); f(w.pRecCnt, 1); f(w.mKeys, w.maxOvPart); f(w.mOrd, w.maxOvPart);
+}
+size_t wideHeadWords(const T4Wide &w) { return (size_t)(w.pcap + 31) / 32; }   // of T4Wide::headBits (pinned), per read slot
 int ensureWide(t4_ctx *c, int reads, int parts, int groups) {
   T4Wide &w = c->wide;
   if (!c->wideInit) {
@@ -318,33 +362,22 @@ int ensureWide(t4_ctx *c, int reads, int parts, int groups) {
     int n = w.maxReads > 0 ? w.maxReads : 64;
     while (n < reads) n *= 2;
     w.maxReads = 0;
-    if ((r = devAlloc(c, &w.seed, 2 * (size_t)n * T4_WIDE_SEEDS))) return r;   // (two of everything: wideHalf)
-    if ((r = devAlloc(c, &w.bounds, 2 * (size_t)n * (T4_WIDE_MAXP + 1)))) return r;
-    if ((r = devAlloc(c, &w.uniqPref, 2 * (size_t)n * (w.pcap + 1)))) return r;
-    if ((r = devAlloc(c, &w.sortTmp, 2 * (size_t)n * 2 * w.pcap))) return r;
-    if ((r = devAlloc(c, &w.requeue, 2 * (size_t)n))) return r;
+    r = T4_OK;
+    widePoolsPerRead(w, [&](auto *&p, size_t per) { if (!r) r = devAlloc(c, &p, 2 * (size_t)n * per); });   // (two of everything: wideHalf)
+    if (r) return r;
     if (c->headBitsHost) (void)hipHostFree(c->headBitsHost);
     c->headBitsHost = nullptr; w.headBits = nullptr;
-    HIPCHK(c, hipHostMalloc(&c->headBitsHost, sizeof(unsigned) * 2 * (size_t)n * ((w.pcap + 31) / 32), hipHostMallocMapped));
+    HIPCHK(c, hipHostMalloc(&c->headBitsHost, sizeof(unsigned) * 2 * (size_t)n * wideHeadWords(w), hipHostMallocMapped));
     HIPCHK(c, hipHostGetDevicePointer((void **)&w.headBits, c->headBitsHost, 0));
     w.maxReads = n;
   }
   if (parts > w.maxPart) {
     int n = w.maxPart > 0 ? w.maxPart : wideEnv("T4_WIDE_PARTS", 1024);
     while (n < parts) n *= 2;
-    const size_t n2 = 2 * (size_t)n;
     w.maxPart = 0;
-    if ((r = devAlloc(c, &w.pCnt, n2))) return r;
-    if ((r = devAlloc(c, &w.pRead, n2))) return r;
-    if ((r = devAlloc(c, &w.pKeys, n2 * w.pcap))) return r;
-    if ((r = devAlloc(c, &w.gSize, n2 * w.pcap))) return r;
-    if ((r = devAlloc(c, &w.gInfo, n2 * w.pcap))) return r;
-    if ((r = devAlloc(c, &w.gCount, n2 * 4))) return r;
-    if ((r = devAlloc(c, &w.gOff, n2 * 2))) return r;
-    if ((r = devAlloc(c, &w.pRec, n2 * w.maxOvPart * 10))) return r;
-    if ((r = devAlloc(c, &w.pRecCnt, n2))) return r;
-    if ((r = devAlloc(c, &w.mKeys, n2 * w.maxOvPart))) return r;
-    if ((r = devAlloc(c, &w.mOrd, n2 * w.maxOvPart))) return r;
+    r = T4_OK;
+    widePoolsPerPart(w, [&](auto *&p, size_t per) { if (!r) r = devAlloc(c, &p, 2 * (size_t)n * per); });
+    if (r) return r;
     w.maxPart = n;
   }
   if (groups > w.grpCap) {
@@ -364,9 +397,9 @@ T4Wide wideHalf(const t4_ctx *c, int half) {
   T4Wide w = c->wide;
   if (!half) return w;
   const size_t R = (size_t)w.maxReads, P = (size_t)w.maxPart;
-  w.seed += R * T4_WIDE_SEEDS; w.bounds += R * (T4_WIDE_MAXP + 1); w.uniqPref += R * (w.pcap + 1); w.sortTmp += R * 2 * w.pcap; w.requeue += R; w.headBits += R * ((w.pcap + 31) / 32);
-  w.pCnt += P; w.pRead += P; w.pKeys += P * w.pcap; w.gSize += P * w.pcap; w.gInfo += P * w.pcap; w.gCount += P * 4; w.gOff += P * 2;
-  w.pRec += P * w.maxOvPart * 10; w.pRecCnt += P; w.mKeys += P * w.maxOvPart; w.mOrd += P * w.maxOvPart;
+  widePoolsPerRead(w, [&](auto *&p, size_t per) { p += R * per; });
+  widePoolsPerPart(w, [&](auto *&p, size_t per) { p += P * per; });
+  w.headBits += R * wideHeadWords(w);
   w.grpPool += w.grpCap;
   return w;
 }
@@ -1739,9 +1772,22 @@ namespace {
 // (per-barcode images: reads meet a handful of contigs, so the first launch is the 1024-hit tier at 6 groups / CU).
 // On return counts[i] records of read i start at index base[i] of ov / ext / ret (valid until the next call on this ctx).
 struct AqResult { const int32_t *counts, *base; const t4_overlap *ov, *ext; const int32_t *ret; };
+double secondsSince(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 // tierHint (nullable, in/out): nonzero = the read is known to outgrow the LDS tiers, it is launched on the global-scratch tier
 // at once, on a second stream beside the LDS tier; on return nonzero for every read the global-scratch tier served.
 int aqLaunch(t4_ctx *c);
+// a blob's device copy and its pinned, mapped twin on the host: room for twice what the call needs when they have to grow
+int growBlob(t4_ctx *c, size_t need, size_t *cap, unsigned char **dev, unsigned char **host, unsigned char **hostDev) {
+  if (need <= *cap) return T4_OK;
+  if (*dev) (void)hipFree(*dev);
+  if (*host) (void)hipHostFree(*host);
+  *dev = nullptr; *host = nullptr;
+  HIPCHK(c, hipMalloc(dev, need * 2));
+  HIPCHK(c, hipHostMalloc(host, need * 2, hipHostMallocMapped));
+  HIPCHK(c, hipHostGetDevicePointer((void **)hostDev, *host, 0));
+  *cap = need * 2;
+  return T4_OK;
+}
 int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const int32_t *viewOf, bool smallFirst, int n, const char *bases,
             const int64_t *offsets, const int32_t *barcodes, const int32_t *strands, int skip_repeats, const double *factors,
             unsigned char *tierHint = nullptr, bool lean = false, const int32_t *onlySeq = nullptr, const int32_t *forceMin = nullptr, int wantCands = 0) {
@@ -1759,71 +1805,47 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   q.base = base; q.views = views; q.hasViewOf = viewOf != nullptr; q.smallFirst = smallFirst; q.n = n; q.skipRepeats = skip_repeats; q.tierHint = tierHint; q.attempt = 0;
   const int wpk = (maxLen + 15) / 16, wnm = (maxLen + 31) / 32;
   q.wpk = wpk; q.wnm = wnm;
-  // input blob: pk | nm | len | barcode | strand | list(iota) | viewOf | factor
-  // header blob: counts | status | next1 | next2 | outBase | ticks | statistics-stable flags | tail{overflow1, overflow2, hits, pool cursor}
-  auto al8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
-  q.oPk = 0; q.oNm = al8(q.oPk + sizeof(unsigned) * (size_t)n * wpk); q.oLen = al8(q.oNm + sizeof(unsigned) * (size_t)n * wnm);
-  q.oBc = al8(q.oLen + sizeof(int) * (size_t)n); q.oSt = al8(q.oBc + sizeof(int) * (size_t)n); q.oLs = al8(q.oSt + sizeof(int) * (size_t)n);
-  q.oVw = al8(q.oLs + sizeof(int) * (size_t)n); q.oFa = al8(q.oVw + sizeof(int) * (size_t)n); q.oOnly = al8(q.oFa + sizeof(double) * (size_t)n);
-  q.oForce = al8(q.oOnly + sizeof(int) * (size_t)n);
-  // (armed restricted re-queries of reads with long lists: two words per read and the head bitmaps, beside oOnly / oForce; nothing without them)
+  // (armed restricted re-queries of reads with long lists: two words per read and the head bitmaps; nothing without them)
   q.hasArm = false;
   if (!c->armWords.empty()) {
     if (!onlySeq || c->armWords.size() != 2 * (size_t)n) { c->armWords.clear(); c->armHead.clear(); return fail(c, T4_ERR_ARG, "t4_add_query_arm_long_lists armed %d reads; the call that follows has %d%s", (int)(c->armWords.size() / 2), n, onlySeq ? "" : " and no restricted re-query"); }
     q.hasArm = true;
   }
-  q.oArm = al8(q.oForce + sizeof(int) * (size_t)n); q.oHead = al8(q.oArm + (q.hasArm ? sizeof(int) * 2 * (size_t)n : 0));
-  q.oCs = al8(q.oHead + (q.hasArm ? sizeof(unsigned) * c->armHead.size() : 0));
-  q.oWide = al8(q.oCs + sizeof(T4CandArgs)); q.hasOnly = onlySeq != nullptr; q.hasForce = forceMin != nullptr; q.wantCands = (wantCands & 1) != 0; q.keepExtAux = (wantCands & 2) != 0;
-  q.oWideA = al8(q.oWide + sizeof(T4Wide)); q.inBytes = al8(q.oWideA + sizeof(T4Wide));
-  q.pCnt = 0; q.pSta = al8(q.pCnt + sizeof(int) * (size_t)n); q.pNext = al8(q.pSta + sizeof(int) * (size_t)n);
-  q.pNext2 = al8(q.pNext + sizeof(int) * (size_t)n); q.pBase = al8(q.pNext2 + sizeof(int) * (size_t)n);
-  q.pTick = al8(q.pBase + sizeof(int) * (size_t)n); q.pStab = al8(q.pTick + sizeof(int) * (size_t)n); q.pAux = al8(q.pStab + sizeof(int) * (size_t)n);
-  q.pN4 = al8(q.pAux + sizeof(int) * (size_t)n); q.pCb = al8(q.pN4 + sizeof(int) * (size_t)n); q.pCc = al8(q.pCb + sizeof(int) * (size_t)n);
-  q.pS8 = al8(q.pCc + sizeof(int) * (size_t)n); q.pRor = al8(q.pS8 + sizeof(int) * T4_QSTATS * (size_t)n); q.pTail = al8(q.pRor + (q.hasArm ? sizeof(int) * (size_t)n : 0));   // tail: overflow1 | overflow2 | hits (8 B) | pool cursor | dir overflow | cand cursor | cand overflow | reads deferred to extendKernel
-  const size_t nW = (size_t)n * (skip_repeats ? 2 : 1);   // (a first pass that finds nothing leaves its slot and takes a new one in the second sweep)
+  q.hasOnly = onlySeq != nullptr; q.hasForce = forceMin != nullptr; q.wantCands = (wantCands & 1) != 0; q.keepExtAux = (wantCands & 2) != 0;
+  const size_t N = (size_t)n, nW = N * (skip_repeats ? 2 : 1);   // (a first pass that finds nothing leaves its slot and takes a new one in the second sweep)
   q.nWideSlots = (int)nW;
-  q.pWctl = q.pTail + 48; q.pWplan = q.pWctl + 32; q.pWstat = al8(q.pWplan + sizeof(T4WidePlan) * nW);
-  q.pWctlA = al8(q.pWstat + sizeof(int) * T4_WIDE_STAT * nW); q.pWplanA = q.pWctlA + 32; q.pWstatA = al8(q.pWplanA + sizeof(T4WidePlan) * nW);
-  q.outBytes = al8(q.pWstatA + sizeof(int) * T4_WIDE_STAT * nW);
+  // the two blobs, field by field in the order they lie in memory (a field that does not apply to the call has no elements)
+  AqInput &in = q.in;
+  in.header = false; in.bytes = 0;
+  in.add(in.pk, N * wpk); in.add(in.nm, N * wnm); in.add(in.len, N); in.add(in.barcode, N); in.add(in.strand, N); in.add(in.list, N); in.add(in.viewOf, N); in.add(in.factor, N);
+  in.add(in.onlySeq, N); in.add(in.forceMin, N); in.add(in.arm, q.hasArm ? 2 * N : 0); in.add(in.head, q.hasArm ? c->armHead.size() : 0);
+  in.add(in.cs, 1); in.add(in.wide[0], 1); in.add(in.wide[1], 1);
+  AqHeader &hdr = q.hdr;
+  hdr.header = true; hdr.bytes = 0;
+  hdr.add(hdr.counts, N); hdr.add(hdr.status, N); hdr.add(hdr.next, N); hdr.add(hdr.next2, N); hdr.add(hdr.outBase, N); hdr.add(hdr.ticks, N); hdr.add(hdr.stable, N);
+  hdr.add(hdr.aux, N); hdr.add(hdr.n4, N); hdr.add(hdr.candBase, N); hdr.add(hdr.candCnt, N); hdr.add(hdr.stats8, T4_QSTATS * N); hdr.add(hdr.rorInfo, q.hasArm ? N : 0);
+  hdr.add(hdr.tail, 1);
+  for (auto &h : hdr.wide) { hdr.add(h.ctl, T4_WC_WORDS); hdr.add(h.plan, nW); hdr.add(h.stat, T4_WIDE_STAT * nW); }
   q.wideSafety = c->wideSafetyKeep;
-  if (q.inBytes > c->aqInBytes) {
-    if (c->aqIn) (void)hipFree(c->aqIn);
-    if (c->aqInHost) (void)hipHostFree(c->aqInHost);
-    c->aqIn = nullptr; c->aqInHost = nullptr;
-    HIPCHK(c, hipMalloc(&c->aqIn, q.inBytes * 2));
-    HIPCHK(c, hipHostMalloc(&c->aqInHost, q.inBytes * 2, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer((void **)&c->aqInHostDev, c->aqInHost, 0));
-    c->aqInBytes = q.inBytes * 2;
-  }
-  if (q.outBytes > c->aqOutBytes) {
-    if (c->aqOut) (void)hipFree(c->aqOut);
-    if (c->aqOutHost) (void)hipHostFree(c->aqOutHost);
-    c->aqOut = nullptr; c->aqOutHost = nullptr;
-    HIPCHK(c, hipMalloc(&c->aqOut, q.outBytes * 2));
-    HIPCHK(c, hipHostMalloc(&c->aqOutHost, q.outBytes * 2, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer((void **)&c->aqOutHostDev, c->aqOutHost, 0));
-    c->aqOutBytes = q.outBytes * 2;
-  }
-  auto tNow = [] { return std::chrono::steady_clock::now(); };
-  auto tSince = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-  auto tp0 = tNow();
-  unsigned char *h = c->aqInHost;
-  memset(h, 0, q.inBytes);
+  int r;
+  if ((r = growBlob(c, in.bytes, &c->aqInBytes, &c->aqIn, &c->aqInHost, &c->aqInHostDev)) || (r = growBlob(c, hdr.bytes, &c->aqOutBytes, &c->aqOut, &c->aqOutHost, &c->aqOutHostDev))) return r;
+  const auto tp0 = std::chrono::steady_clock::now();
+  memset(c->aqInHost, 0, q.in.bytes);
   if (q.hasArm) {   // (consumed: the arming holds for this call alone)
-    memcpy(h + q.oArm, c->armWords.data(), sizeof(int) * c->armWords.size());
-    if (!c->armHead.empty()) memcpy(h + q.oHead, c->armHead.data(), sizeof(unsigned) * c->armHead.size());
+    std::copy(c->armWords.begin(), c->armWords.end(), q.in.arm.stage(c));
+    std::copy(c->armHead.begin(), c->armHead.end(), q.in.head.stage(c));
     c->armWords.clear(); c->armHead.clear();
   }
-  unsigned *pk = (unsigned *)(h + q.oPk), *nm = (unsigned *)(h + q.oNm);
-  int *len = (int *)(h + q.oLen), *bc = (int *)(h + q.oBc), *st = (int *)(h + q.oSt), *ls = (int *)(h + q.oLs), *vw = (int *)(h + q.oVw);
-  double *fa = (double *)(h + q.oFa);
+  unsigned *pk = q.in.pk.stage(c), *nm = q.in.nm.stage(c);
+  int *len = q.in.len.stage(c), *bc = q.in.barcode.stage(c), *st = q.in.strand.stage(c), *ls = q.in.list.stage(c), *vw = q.in.viewOf.stage(c);
+  int *only = q.in.onlySeq.stage(c), *force = q.in.forceMin.stage(c);
+  double *fa = q.in.factor.stage(c);
   for (int i = 0; i < n; ++i) {
     const char *s = bases + offsets[i];
     int l = (int)(offsets[i + 1] - offsets[i]);
     len[i] = l; bc[i] = barcodes ? barcodes[i] : -1; st[i] = strands[i]; fa[i] = factors[i]; vw[i] = viewOf ? viewOf[i] : 0;
-    ((int *)(h + q.oOnly))[i] = onlySeq ? onlySeq[i] : -1;
-    ((int *)(h + q.oForce))[i] = forceMin ? forceMin[i] : 0;
+    only[i] = onlySeq ? onlySeq[i] : -1;
+    force[i] = forceMin ? forceMin[i] : 0;
     unsigned *p = pk + (size_t)i * wpk, *qn = nm + (size_t)i * wnm;
     for (int j = 0; j < l; ++j) {
       int v = nucNum(s[j]);
@@ -1854,36 +1876,43 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   for (int i = 0; i < n; ++i) if (!direct(i)) ls[nFirst++] = i;
   for (int i = 0; i < n; ++i) if (direct(i)) ls[nFirst + nDirect++] = i;
   q.nFirst = nFirst; q.nDirect = nDirect;
-  c->aqSecPack += tSince(tp0);
-  const int r = aqLaunch(c);
+  c->aqSecPack += secondsSince(tp0);
+  r = aqLaunch(c);
   if (r == T4_OK) q.active = true;
   return r;
 }
 
-// the wide query of the reads the round's query kernel deferred, on the ctx's stream, once the header of the call is on the host
-// (the counts of deferred reads and their partitions size the grids)
-void aqLaunchDeferredWide(t4_ctx *c) {
-  AqCall &q = c->aq;
-  T4Wide w;
-  memcpy(&w, c->aqInHost + q.oWide, sizeof w);
-  const int cus = c->cus > 0 ? c->cus : 1;
-  // The grids are persistent (any size serves any number of reads / partitions); an empty grid of several hundred 100 KB-LDS workgroups
-  // still takes microseconds to come and go.
-  auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; };
-  const int *ctl = (const int *)(c->aqOutHost + q.pWctl);
-  const int gParts = clampi(ctl[1] + 1, 4, cus * 2), gReads = clampi(ctl[0], 1, cus < 64 ? cus : 64);
-  hipLaunchKernelGGL(t4k::wideScatterKernel, dim3(clampi(8 * gParts, 16, cus * 8)), dim3(256), 0, c->stream, q.base, w);   // (a partition is planned for four of the kernel's chunks)
-  hipLaunchKernelGGL((t4k::wideSortKernel<8192>), dim3(gParts), dim3(512), 0, c->stream, q.base, w);
-  hipLaunchKernelGGL(t4k::wideStatsKernel, dim3(gReads), dim3(512), 0, c->stream, q.base, w);
-  hipLaunchKernelGGL((t4k::wideChainKernel<8192, 1 << T4_WIDE_OVBITS>), dim3(gParts < cus ? gParts : cus), dim3(512), 0, c->stream, q.base, q.bv, q.wk, q.qa, w);
-  hipLaunchKernelGGL(t4k::wideMergeKernel, dim3(gReads), dim3(512), 0, c->stream, q.base, q.bv, q.wk, q.qa, w);
+// The five kernels of the wide query behind its seed stage, on `stream`. The grids are persistent (any size serves any number of
+// reads / partitions; an empty grid of several hundred 100 KB-LDS workgroups still takes microseconds to come and go): the caller
+// sizes them by what it knows of the reads (wideGrid*), wk is the work description the chain and merge kernels score with.
+int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+int wideCus(const t4_ctx *c) { return c->cus > 0 ? c->cus : 1; }
+int wideGridParts(const t4_ctx *c, int want) { return clampi(want, 4, wideCus(c) * 2); }
+int wideGridReads(const t4_ctx *c, int want) { return clampi(want, 1, wideCus(c) < 64 ? wideCus(c) : 64); }
+void launchWideSeed(t4_ctx *c, hipStream_t stream, const T4Wide &w, const T4Work &wk, const int *list, int nList, int firstPass) {   // the seed stage of the reads `list` (device)
+  const AqCall &q = c->aq;
+  hipLaunchKernelGGL(t4k::wideSeedKernel, dim3(nList < wideCus(c) ? nList : wideCus(c)), dim3(512), 0, stream, q.base, q.bv, wk, q.qa, w, list, nList, firstPass);
+}
+void launchWide(t4_ctx *c, hipStream_t stream, const T4Wide &w, const T4Work &wk, int gParts, int gReads) {
+  const AqCall &q = c->aq;
+  const int cus = wideCus(c);
+  hipLaunchKernelGGL(t4k::wideScatterKernel, dim3(clampi(8 * gParts, 16, cus * 8)), dim3(256), 0, stream, q.base, w);   // (a partition is planned for four of the kernel's chunks)
+  hipLaunchKernelGGL((t4k::wideSortKernel<8192>), dim3(gParts), dim3(512), 0, stream, q.base, w);
+  hipLaunchKernelGGL(t4k::wideStatsKernel, dim3(gReads), dim3(512), 0, stream, q.base, w);
+  hipLaunchKernelGGL((t4k::wideChainKernel<8192, 1 << T4_WIDE_OVBITS>), dim3(gParts < cus ? gParts : cus), dim3(512), 0, stream, q.base, q.bv, wk, q.qa, w);
+  hipLaunchKernelGGL(t4k::wideMergeKernel, dim3(gReads), dim3(512), 0, stream, q.base, q.bv, wk, q.qa, w);
+}
+// extendKernel over the records of the result pool from `firstRec` on, spread over the chip
+int launchExtend(t4_ctx *c, int firstRec) {
+  const AqCall &q = c->aq;
+  hipLaunchKernelGGL(t4k::extendKernel, dim3(c->cus * 16), dim3(64), 0, c->stream, q.base, q.bv, q.qa, firstRec < c->aqPoolCap ? firstRec : c->aqPoolCap);
+  HIPCHK(c, hipGetLastError());
+  return T4_OK;
 }
 int aqLaunchEpilogue(t4_ctx *c) {   // the header block into pinned host memory, then the call's sequence number into the word the host polls (aqEpilogueKernel)
   AqCall &q = c->aq;
-  const unsigned long long outW = q.outBytes >> 3;
-  int grid = (int)((outW + 4095) / 4096);
-  if (grid < 1) grid = 1;
-  if (grid > 64) grid = 64;
+  const unsigned long long outW = q.hdr.bytes >> 3;
+  const int grid = clampi((int)((outW + 4095) / 4096), 1, 64);
   ++c->aqSeq;
   if (c->aqSeq == 0) c->aqSeq = 1;
   hipLaunchKernelGGL(t4k::aqEpilogueKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned long long *)c->aqOut, (unsigned long long *)c->aqOutHostDev, outW,
@@ -1899,10 +1928,8 @@ int aqLaunch(t4_ctx *c) {
   const bool smallFirst = q.smallFirst;
   int r;
   if (!c->aqPool) {
-    const int poolCap0 = c->aqEnv.poolCap;   // testing aid: a small pool forces the grow-and-repeat path
-    if (!c->aqPoolCap) c->aqPoolCap = poolCap0 > 0 ? poolCap0 : 1 << 16;
-    const size_t rec = (size_t)c->aqPoolCap;
-    HIPCHK(c, hipHostMalloc(&c->aqPool, rec * (2 * sizeof(t4_overlap) + sizeof(int32_t)), hipHostMallocMapped));
+    if (!c->aqPoolCap) c->aqPoolCap = c->aqEnv.poolCap > 0 ? c->aqEnv.poolCap : 1 << 16;   // (testing aid: a small pool forces the grow-and-repeat path)
+    HIPCHK(c, hipHostMalloc(&c->aqPool, (size_t)c->aqPoolCap * (2 * sizeof(t4_overlap) + sizeof(int32_t)), hipHostMallocMapped));
     HIPCHK(c, hipHostGetDevicePointer((void **)&c->aqPoolDev, c->aqPool, 0));
   }
   const size_t rec = (size_t)c->aqPoolCap;
@@ -1916,25 +1943,25 @@ int aqLaunch(t4_ctx *c) {
   auto lapL = [&](int i) { const auto t = std::chrono::steady_clock::now(); c->aqSecLaunch[i] += std::chrono::duration<double>(t - tl_).count(); tl_ = t; };
   if (q.wide) {
     if ((r = ensureWide(c, q.nWideSlots, 1, 1))) return r;
-    T4Wide w = wideHalf(c, 0), wa = wideHalf(c, 1);
-    w.enabled = 1; w.safetyNum = q.wideSafety; w.firstRead = w.firstPart = 0;
-    // Reads of up to T4_WIDE_MIN_HITS emitted hits stay with one workgroup (LDS tier, then its slice of global scratch inside the same
-    // launch, beside the other reads of the round): the wide query's kernels run behind the launch and cost a round about 0.25 ms
-    // whatever the read is (profiles/r04b-h); from the LDS tier.s capacity on it beats one workgroup.s global scratch (C2 122 -> 93 s, profiles/r04h_*). The testing aid T4_AQ_CAP_LIMIT lowers
-    // the threshold with the LDS tier's capacity.
-    { const int lim = c->aqEnv.capLimit; w.minHits = lim > 0 ? lim : c->aqEnv.wideMinHits; }
-    w.ctl = (int *)(c->aqOut + q.pWctl); w.plan = (T4WidePlan *)(c->aqOut + q.pWplan); w.stat = (int *)(c->aqOut + q.pWstat);
-    memcpy(c->aqInHost + q.oWide, &w, sizeof w);
-    wa.enabled = 1; wa.safetyNum = w.safetyNum; wa.minHits = w.minHits; wa.firstRead = wa.firstPart = 0;
-    wa.ctl = (int *)(c->aqOut + q.pWctlA); wa.plan = (T4WidePlan *)(c->aqOut + q.pWplanA); wa.stat = (int *)(c->aqOut + q.pWstatA);
-    memcpy(c->aqInHost + q.oWideA, &wa, sizeof wa);
+    for (int half = 0; half < 2; ++half) {
+      T4Wide w = wideHalf(c, half);
+      w.enabled = 1; w.safetyNum = q.wideSafety; w.firstRead = w.firstPart = 0;
+      // Reads of up to T4_WIDE_MIN_HITS emitted hits stay with one workgroup (LDS tier, then its slice of global scratch inside the same
+      // launch, beside the other reads of the round): the wide query's kernels run behind the launch and cost a round about 0.25 ms
+      // whatever the read is (profiles/r04b-h); from the LDS tier's capacity on it beats one workgroup's global scratch (C2 122 -> 93 s,
+      // profiles/r04h_*). The testing aid T4_AQ_CAP_LIMIT lowers the threshold with the LDS tier's capacity.
+      w.minHits = c->aqEnv.capLimit > 0 ? c->aqEnv.capLimit : c->aqEnv.wideMinHits;
+      w.ctl = q.hdr.wide[half].ctl.dev(c); w.plan = q.hdr.wide[half].plan.dev(c); w.stat = q.hdr.wide[half].stat.dev(c);
+      *q.in.wide[half].stage(c) = w;
+    }
   }
+  T4AqTail *const tail = q.hdr.tail.dev(c);
   {
     T4CandArgs cs;
     memset(&cs, 0, sizeof cs);
-    cs.stats8 = (int *)(c->aqOut + q.pS8);
-    if (q.hasForce) cs.forceMin = (const int *)(c->aqIn + q.oForce);
-    if (q.hasArm) { cs.rorArm = (const int *)(c->aqIn + q.oArm); cs.rorHead = (const unsigned *)(c->aqIn + q.oHead); cs.rorInfo = (int *)(c->aqOut + q.pRor); }
+    cs.stats8 = q.hdr.stats8.dev(c);
+    if (q.hasForce) cs.forceMin = q.in.forceMin.dev(c);
+    if (q.hasArm) { cs.rorArm = q.in.arm.dev(c); cs.rorHead = q.in.head.dev(c); cs.rorInfo = q.hdr.rorInfo.dev(c); }
     if (q.keepExtAux) {   // (sized with the pool: a call repeated with a larger pool comes through here again)
       if (c->aqExtAuxCap < c->aqPoolCap) {
         c->aqExtAuxCap = 0;
@@ -1944,42 +1971,36 @@ int aqLaunch(t4_ctx *c) {
       cs.extAux = c->aqExtAux;
     }
     if (q.wantCands) {
-      cs.candOut = c->candPoolDev; cs.candCap = c->candCap; cs.candCursor = (unsigned *)(c->aqOut + q.pTail + 32); cs.candOverflow = (int *)(c->aqOut + q.pTail + 36);
-      cs.candBase = (int *)(c->aqOut + q.pCb); cs.candCnt = (int *)(c->aqOut + q.pCc);
+      cs.candOut = c->candPoolDev; cs.candCap = c->candCap; cs.candCursor = &tail->candCursor; cs.candOverflow = &tail->candOverflow;
+      cs.candBase = q.hdr.candBase.dev(c); cs.candCnt = q.hdr.candCnt.dev(c);
     }
-    memcpy(c->aqInHost + q.oCs, &cs, sizeof cs);
+    *q.in.cs.stage(c) = cs;
   }
   lapL(0);
   {   // input blob into device memory, header block zeroed (counts, status, overflow lists, bases, tail): one kernel, no copy engine (t4_kernels.h: aqPrologueKernel)
-    const unsigned long long inW = q.inBytes >> 3, outW = q.outBytes >> 3;
+    const unsigned long long inW = q.in.bytes >> 3, outW = q.hdr.bytes >> 3;
     const unsigned long long most = inW > outW ? inW : outW;
-    int grid = (int)((most + 2047) / 2048);
-    if (grid < 1) grid = 1;
-    if (grid > c->cus * 4) grid = c->cus * 4;
+    const int grid = clampi((int)((most + 2047) / 2048), 1, c->cus * 4);
     hipLaunchKernelGGL(t4k::aqPrologueKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned long long *)c->aqInHostDev, (unsigned long long *)c->aqIn, inW,
                        (unsigned long long *)c->aqOut, outW);
     HIPCHK(c, hipGetLastError());
   }
   lapL(1);
   T4BatchView &bv = q.bv;
-  bv.pk = (const unsigned *)(c->aqIn + q.oPk); bv.nm = (const unsigned *)(c->aqIn + q.oNm); bv.len = (const int *)(c->aqIn + q.oLen);
-  bv.barcode = (const int *)(c->aqIn + q.oBc); bv.wpk = q.wpk; bv.wnm = q.wnm; bv.n = n;
+  bv.pk = q.in.pk.dev(c); bv.nm = q.in.nm.dev(c); bv.len = q.in.len.dev(c);
+  bv.barcode = q.in.barcode.dev(c); bv.wpk = q.wpk; bv.wnm = q.wnm; bv.n = n;
   T4QueryArgs &qa = q.qa;
   memset(&qa, 0, sizeof qa);
   qa.mode = 4; qa.skipRepeats = q.skipRepeats; qa.maxPerRead = 0;
-  qa.counts = (int *)(c->aqOut + q.pCnt);
+  qa.counts = q.hdr.counts.dev(c);
   qa.out = (T4OverlapOut *)c->aqPoolDev; qa.outExt = qa.out + rec; qa.ret = (int *)(qa.outExt + rec);
-  qa.outBase = (int *)(c->aqOut + q.pBase); qa.poolCursor = (unsigned *)(c->aqOut + q.pTail + 24); qa.poolCap = c->aqPoolCap;
-  qa.strandPerRead = (const int *)(c->aqIn + q.oSt); qa.factorPerRead = (const double *)(c->aqIn + q.oFa);
-  qa.readTicks = (int *)(c->aqOut + q.pTick);
-  qa.statsStable = (int *)(c->aqOut + q.pStab);
-  qa.aux = (int *)(c->aqOut + q.pAux); qa.n4 = (int *)(c->aqOut + q.pN4);
-  if (q.hasOnly) qa.onlySeq = (const int *)(c->aqIn + q.oOnly);
-  {   // statistics words always; candidate records when asked for (the struct travels in the input blob: filled before the H2D copy above)
-    qa.cs = (const T4CandArgs *)(c->aqIn + q.oCs);
-  }
+  qa.outBase = q.hdr.outBase.dev(c); qa.poolCursor = &tail->poolCursor; qa.poolCap = c->aqPoolCap;
+  qa.strandPerRead = q.in.strand.dev(c); qa.factorPerRead = q.in.factor.dev(c);
+  qa.readTicks = q.hdr.ticks.dev(c); qa.statsStable = q.hdr.stable.dev(c); qa.aux = q.hdr.aux.dev(c); qa.n4 = q.hdr.n4.dev(c);
+  if (q.hasOnly) qa.onlySeq = q.in.onlySeq.dev(c);
+  qa.cs = q.in.cs.dev(c);   // statistics words always; candidate records when asked for (the struct travels in the input blob: filled before the prologue above)
   qa.leanExt = q.lean ? 1 : 0;
-  if (q.views) { qa.views = q.views; qa.viewOf = (const int *)(c->aqIn + q.oVw); }
+  if (q.views) { qa.views = q.views; qa.viewOf = q.in.viewOf.dev(c); }
   // one big set: the ExtendOverlap calls of reads with more than this many overlaps run in their own launch (0: never)
   int deferMin = c->aqEnv.extendDefer;   // testing aid
   if (q.wide && deferMin <= 0) deferMin = 16;   // the wide query leaves every ExtendOverlap to extendKernel
@@ -1987,11 +2008,8 @@ int aqLaunch(t4_ctx *c) {
   q.extendLater = extendLater;
   if (extendLater) {
     if (c->aqRecCap < c->aqPoolCap) {
-      if (c->aqRecDev) (void)hipFree(c->aqRecDev);
-      if (c->aqRecRead) (void)hipFree(c->aqRecRead);
-      c->aqRecDev = nullptr; c->aqRecRead = nullptr;
-      HIPCHK(c, hipMalloc(&c->aqRecDev, sizeof(T4OverlapOut) * (size_t)c->aqPoolCap));
-      HIPCHK(c, hipMalloc(&c->aqRecRead, sizeof(int) * (size_t)c->aqPoolCap));
+      c->aqRecCap = 0;
+      if ((r = devAlloc(c, &c->aqRecDev, (size_t)c->aqPoolCap)) || (r = devAlloc(c, &c->aqRecRead, (size_t)c->aqPoolCap))) return r;
       c->aqRecCap = c->aqPoolCap;
     }
     qa.extendLater = deferMin; qa.outDev = c->aqRecDev; qa.recRead = c->aqRecRead;
@@ -2004,12 +2022,12 @@ int aqLaunch(t4_ctx *c) {
   if ((r = ensureScratch(c, (grid0 > c->cus * 2 ? grid0 : c->cus * 2) * threads + (q.wide ? (nDirect > 0 ? c->cus * 512 : 0) : nDirect * G_THREADS)))) return r;
   T4Work &wk = q.wk;
   memset(&wk, 0, sizeof wk);
-  wk.list = (const int *)(c->aqIn + q.oLs); wk.nList = nFirst;
-  wk.nextList = (int *)(c->aqOut + q.pNext); wk.nextCount = (int *)(c->aqOut + q.pTail);
-  wk.status = (int *)(c->aqOut + q.pSta); wk.hitCounter = (unsigned long long *)(c->aqOut + q.pTail + 16);
+  wk.list = q.in.list.dev(c); wk.nList = nFirst;
+  wk.nextList = q.hdr.next.dev(c); wk.nextCount = &tail->overflow;
+  wk.status = q.hdr.status.dev(c); wk.hitCounter = &tail->hits;
   wk.dpRows = c->dpRows; wk.dpDir = c->dpDir;
   wk.capLimit = c->aqEnv.capLimit;   // testing aid
-  wk.wide = q.wide ? (const T4Wide *)(c->aqIn + q.oWide) : nullptr;
+  wk.wide = q.wide ? q.in.wide[0].dev(c) : nullptr;
   if (!smallFirst && (r = ensureGlobalTier(c, grid0 + (q.wide ? 0 : nDirect)))) return r;   // before anything of this call runs: growing it frees the old arrays
   lapL(0);
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
@@ -2019,23 +2037,15 @@ int aqLaunch(t4_ctx *c) {
     HIPCHK(c, hipEventRecord(c->evIn, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evIn, 0));
     T4Work wd = wk;
-    wd.list = (const int *)(c->aqIn + q.oLs) + nFirst; wd.nList = nDirect; wd.nextList = nullptr; wd.nextCount = nullptr;
+    wd.list = wk.list + nFirst; wd.nList = nDirect; wd.nextList = nullptr; wd.nextCount = nullptr;
     wd.dpRows = c->dpRows + (size_t)((grid0 > c->cus * 2 ? grid0 : c->cus * 2) * threads / 64) * (6 * T4_ROWW * 64);
     wd.dpDir = c->dpDir + (size_t)(grid0 > c->cus * 2 ? grid0 : c->cus * 2) * threads * T4_DIR_BYTES;
     if (q.wide) {
       // the wide query of the reads known to be heavy, beside the round's query kernel: seed stage, then the same five kernels on the
       // second half of the pools (wideHalf) and their own stretch of the DP scratch
-      T4Wide wa;
-      memcpy(&wa, c->aqInHost + q.oWideA, sizeof wa);
-      const int cus = c->cus > 0 ? c->cus : 1;
-      auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; };
-      const int gParts = clampi(2 * c->wideRecentParts + 4 * nDirect + 4, 4, cus * 2), gReads = clampi(nDirect, 1, cus < 64 ? cus : 64);
-      hipLaunchKernelGGL(t4k::wideSeedKernel, dim3(nDirect < cus ? nDirect : cus), dim3(512), 0, c->stream2, q.base, bv, wd, qa, wa, wd.list, nDirect, q.skipRepeats ? 1 : 0);
-      hipLaunchKernelGGL(t4k::wideScatterKernel, dim3(clampi(8 * gParts, 16, cus * 8)), dim3(256), 0, c->stream2, q.base, wa);
-      hipLaunchKernelGGL((t4k::wideSortKernel<8192>), dim3(gParts), dim3(512), 0, c->stream2, q.base, wa);
-      hipLaunchKernelGGL(t4k::wideStatsKernel, dim3(gReads), dim3(512), 0, c->stream2, q.base, wa);
-      hipLaunchKernelGGL((t4k::wideChainKernel<8192, 1 << T4_WIDE_OVBITS>), dim3(gParts < cus ? gParts : cus), dim3(512), 0, c->stream2, q.base, bv, wd, qa, wa);
-      hipLaunchKernelGGL(t4k::wideMergeKernel, dim3(gReads), dim3(512), 0, c->stream2, q.base, bv, wd, qa, wa);
+      const T4Wide &wa = *q.in.wide[1].stage(c);
+      launchWideSeed(c, c->stream2, wa, wd, wd.list, nDirect, q.skipRepeats ? 1 : 0);
+      launchWide(c, c->stream2, wa, wd, wideGridParts(c, 2 * c->wideRecentParts + 4 * nDirect + 4), wideGridReads(c, nDirect));
     } else {
       wd.gKeys = c->gKeys; wd.gPairs = c->gPairs; wd.gCand = c->gCand; wd.gOv = c->gOv; wd.gFin = c->gFin; wd.gOrd = c->gOrd;
       wd.gCap = G_CAP; wd.gMaxOv = G_MAXOV;
@@ -2059,19 +2069,12 @@ int aqLaunch(t4_ctx *c) {
     HIPCHK(c, hipGetLastError());
   }
   lapL(3);
-  if (nDirect > 0 && !q.wide) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evG, 0));
+  if (nDirect > 0) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evG, 0));   // the second stream's records are in the pool before the extensions run
+  // The wide query of the reads the launch above deferred. Since round 5 a fresh heavy read is recognised on the host a round ahead and
+  // starts on the second stream, so the query kernel defers a read in one whole-query round of twenty (config C2: 2 434 of 42 654): the
+  // five kernels behind it were five empty grids in the others. They are launched when the header says that a read was deferred (aqEnd).
   q.lazyDone = false; q.lazyStage = false; q.sweep2Done = false;
-  if (q.wide) {
-    // The reads the launch above deferred. Since round 5 a fresh heavy read is recognised on the host a round ahead and starts on the
-    // second stream, so the query kernel defers a read in one whole-query round of twenty (config C2: 2 434 of 42 654): the five kernels
-    // behind it were five empty grids in the others. They are launched when the header says that a read was deferred (aqEnd).
-    if (nDirect > 0) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evG, 0));   // the other pipeline's records are in the pool before the extensions run
-  }
-  if (extendLater) {   // all records of the batch, spread over the chip
-    const int grid = c->cus * 16;
-    hipLaunchKernelGGL(t4k::extendKernel, dim3(grid), dim3(64), 0, c->stream, q.base, bv, qa, 0);
-    HIPCHK(c, hipGetLastError());
-  }
+  if (extendLater && (r = launchExtend(c, 0))) return r;   // all records of the batch
   lapL(4);
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   lapL(5);
@@ -2104,19 +2107,114 @@ int aqDone(t4_ctx *c) {
   return __atomic_load_n(c->aqFlagHost, __ATOMIC_ACQUIRE) == c->aqSeq ? 1 : 0;
 }
 
+// A launch that aqEnd adds to the call once its header is on the host: between the ctx's two events, with the extensions of the
+// records it adds behind it.
+template <class Launch> int aqTimedLaunch(t4_ctx *c, Launch launchIt) {
+  const int recsBefore = (int)c->aq.hdr.tail.host(c)->poolCursor;
+  int r;
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  launchIt();
+  HIPCHK(c, hipGetLastError());
+  if (c->aq.extendLater && (r = launchExtend(c, recsBefore))) return r;
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+  return T4_OK;
+}
+// ... as one more stage of the call (the wide query of deferred reads, the second sweep): a new epilogue behind it, and aqEnd waits again
+template <class Launch> int aqStage(t4_ctx *c, Launch launchIt) {
+  c->aq.lazyStage = true;
+  const int r = aqTimedLaunch(c, launchIt);
+  return r ? r : aqLaunchEpilogue(c);
+}
+// ... as a rerun of reads on the next tier (rare paths, synchronous): the header is copied back and waited for here
+template <class Launch> int aqRerun(t4_ctx *c, Launch launchIt) {
+  int r;
+  if ((r = aqTimedLaunch(c, launchIt))) return r;
+  HIPCHK(c, hipMemcpyAsync(c->aqOutHost, c->aqOut, c->aq.hdr.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  { float ms = 0; if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->aqKernelMs += ms; }
+  return T4_OK;
+}
+// The whole call again, after the caller made room for what overflowed. `pool`: a pinned pool to drop (aqLaunch allocates it anew at
+// the capacity the caller has set).
+int aqRepeat(t4_ctx *c, unsigned char **pool = nullptr) {
+  if (pool) { (void)hipHostFree(*pool); *pool = nullptr; }
+  ++c->aq.attempt;
+  return aqLaunch(c);
+}
+
+// read slots of one half of the wide query that the call filled, by the header on the host
+int wideSlots(const t4_ctx *c, int half) {
+  const int n = c->aq.hdr.wide[half].ctl.host(c)[T4_WC_READS];
+  return n < c->aq.nWideSlots ? n : c->aq.nWideSlots;
+}
+struct WideSlot { int half, slot; };   // (half < 0: none)
+WideSlot findWideSlot(const t4_ctx *c, int read) {   // where the wide query served `read` in the last call
+  for (int half = 0; half < 2; ++half) {
+    const T4WidePlan *plan = c->aq.hdr.wide[half].plan.host(c);
+    for (int s = 0, n = wideSlots(c, half); s < n; ++s) if (plan[s].read == read) return {half, s};
+  }
+  return {-1, 0};
+}
+
+// a pool of the wide query ran out (T4WideFlag bits of both halves): larger pools / finer partitions for the repeat of the call
+int aqWideGrow(t4_ctx *c, int flags) {
+  AqCall &q = c->aq;
+  const int *ctl = q.hdr.wide[0].ctl.host(c), *ctlA = q.hdr.wide[1].ctl.host(c);
+  int r;
+  if (q.attempt >= 12 || (flags & (T4_WF_READS | T4_WF_INTERNAL))) return fail(c, T4_ERR_UNSUPPORTED, "wide query: flags %d after %d attempts", flags, q.attempt);
+  if (flags & T4_WF_PARTS) {
+    const int need = ctl[T4_WC_PARTS] > ctlA[T4_WC_PARTS] ? ctl[T4_WC_PARTS] : ctlA[T4_WC_PARTS];
+    if (need <= c->wide.maxPart) return fail(c, T4_ERR_UNSUPPORTED, "a read of this batch needs more than %d partitions of %d k-mer hits", T4_WIDE_MAXP, c->wide.pcap);
+    if ((r = ensureWide(c, q.nWideSlots, need, 1))) return r;
+  }
+  for (int b = 0; b < 6; ++b) if (flags & (1 << b)) ++c->wideFlagCounts[b];
+  if (flags & (T4_WF_KEYS | T4_WF_OVERLAPS)) {
+    if (q.wideSafety >= 32 * 256) return fail(c, T4_ERR_UNSUPPORTED, "wide query: a contig range of one contig overflows a partition");
+    q.wideSafety *= 2;
+    // keys: the partitions are quantiles of a SAMPLE of the hits' contigs; when a sample misjudged one, the next calls (the same
+    // reads again, mostly) are planned less full as well. Overlaps of a partition: one read's matter (hundreds of short chains in
+    // one contig range) -- finer partitions for this call only.
+    if (flags & T4_WF_KEYS) { c->wideSafetyKeep = q.wideSafety < 128 ? q.wideSafety : 128; c->wideCallsSinceRepeat = 0; }
+  }
+  if ((flags & T4_WF_GROUPS) && (r = ensureWide(c, q.nWideSlots, 1, ctl[T4_WC_GROUPS] > ctlA[T4_WC_GROUPS] ? ctl[T4_WC_GROUPS] : ctlA[T4_WC_GROUPS]))) return r;
+  ++c->wideRetries;
+  return T4_OK;
+}
+// the wide query of a finished call: the ctx's statistics, and the reads to start on the second stream the next time
+void aqWideAccount(t4_ctx *c) {
+  AqCall &q = c->aq;
+  const int *ctl = q.hdr.wide[0].ctl.host(c), *ctlA = q.hdr.wide[1].ctl.host(c);
+  const int requeued = ctl[T4_WC_REQUEUED] + ctlA[T4_WC_REQUEUED];
+  // (slots of first passes that found nothing were retired, T4WidePlan::read < 0: their partitions and dependency records are not counted)
+  int retiredParts[2] = {0, 0}, retiredGroups = 0;
+  for (int half = 0; half < 2 && requeued > 0; ++half) {
+    const T4WidePlan *pl = q.hdr.wide[half].plan.host(c);
+    const int *st = q.hdr.wide[half].stat.host(c);
+    for (int s = 0, ns = wideSlots(c, half); s < ns; ++s) if (pl[s].read < 0) { retiredParts[half] += pl[s].P; retiredGroups += st[(size_t)s * T4_WIDE_STAT + WS_GROUPS]; }
+  }
+  c->wideReads += ctl[T4_WC_READS] + ctlA[T4_WC_READS] - requeued; c->wideParts += ctl[T4_WC_PARTS] + ctlA[T4_WC_PARTS] - retiredParts[0] - retiredParts[1];
+  c->wideGroups += ctl[T4_WC_GROUPS] + ctlA[T4_WC_GROUPS] - retiredGroups;
+  ++c->wideCalls; if (ctl[T4_WC_READS] > 0) ++c->wideCallsDeferred; if (ctlA[T4_WC_READS] > 0) ++c->wideCallsDirect;
+  if (ctl[T4_WC_READS] + ctlA[T4_WC_READS] > 0 && ++c->wideCallsSinceRepeat >= 2048 && c->wideSafetyKeep > 32) { c->wideSafetyKeep /= 2; c->wideCallsSinceRepeat = 0; }
+  { const int parts = ctl[T4_WC_PARTS] - retiredParts[0]; c->wideRecentParts = parts > c->wideRecentParts ? parts : (c->wideRecentParts * 7 + parts) / 8; }
+  if (!q.tierHint) return;
+  for (int half = 0; half < 2; ++half) {   // remembered by the caller: these reads start on the second stream the next time they are queried
+    const T4WidePlan *pl = q.hdr.wide[half].plan.host(c);
+    for (int s = 0, ns = wideSlots(c, half); s < ns; ++s) if (pl[s].read >= 0 && pl[s].read < q.n) q.tierHint[pl[s].read] = 1;
+  }
+}
+
 int aqEnd(t4_ctx *c, AqResult *res) {
   AqCall &q = c->aq;
   if (!q.active) return fail(c, T4_ERR_STATE, "no AddRead query in flight on this ctx");
   q.active = false;
   (void)hipSetDevice(c->device);
-  auto tNow = [] { return std::chrono::steady_clock::now(); };
-  auto tSince = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
   const int n = q.n;
   const bool smallFirst = q.smallFirst;
-  const size_t pTail = q.pTail, pNext = q.pNext, pNext2 = q.pNext2, outBytes = q.outBytes;
-  T4Work &wk = q.wk;
-  T4QueryArgs &qa = q.qa;
-  T4BatchView &bv = q.bv;
+  const AqHeader &hdr = q.hdr;
+  const T4AqTail *const tail = hdr.tail.host(c);   // (the header on the host: fresh after every wait below)
+  const int *const ctl = hdr.wide[0].ctl.host(c), *const ctlA = hdr.wide[1].ctl.host(c);
+  const T4Work &wk = q.wk;
   int r;
   for (;;) {
     // The caller sits on the ordered chain's critical path: poll for the round's last event before the blocking wait (a wait that
@@ -2132,21 +2230,12 @@ int aqEnd(t4_ctx *c, AqResult *res) {
       if (ee == hipErrorNotReady) { (void)hipEventSynchronize(c->ev[1]); ee = hipEventElapsedTime(&ms, c->ev[0], c->ev[1]); }
       if (ee == hipSuccess) { c->aqKernelMs += ms; c->aqLastMs = q.lazyStage ? c->aqLastMs + ms : ms; }
     }
+    const bool wideClean = q.wide && !ctl[T4_WC_FLAGS] && !ctlA[T4_WC_FLAGS];
     if (q.wide && !q.lazyDone) {   // did the query kernel defer a read? then its wide query runs now, and the extensions of its records behind it
       q.lazyDone = true;
-      const int *ctl0 = (const int *)(c->aqOutHost + q.pWctl);
-      if (ctl0[0] > 0 && !ctl0[2] && !*(const int *)(c->aqOutHost + q.pWctlA + 8)) {
-        const int recsBefore = (int)*(const unsigned *)(c->aqOutHost + pTail + 24);
-        q.lazyStage = true;
-        HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-        aqLaunchDeferredWide(c);
-        HIPCHK(c, hipGetLastError());
-        if (q.extendLater) {
-          hipLaunchKernelGGL(t4k::extendKernel, dim3(c->cus * 16), dim3(64), 0, c->stream, q.base, bv, qa, recsBefore < c->aqPoolCap ? recsBefore : c->aqPoolCap);
-          HIPCHK(c, hipGetLastError());
-        }
-        HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-        if ((r = aqLaunchEpilogue(c))) return r;
+      if (wideClean && ctl[T4_WC_READS] > 0) {   // (the counts of deferred reads and their partitions size the grids)
+        r = aqStage(c, [&] { launchWide(c, c->stream, *q.in.wide[0].stage(c), wk, wideGridParts(c, ctl[T4_WC_PARTS] + 1), wideGridReads(c, ctl[T4_WC_READS])); });
+        if (r) return r;
         continue;
       }
     }
@@ -2155,61 +2244,37 @@ int aqEnd(t4_ctx *c, AqResult *res) {
       // GetOverlapsFromRead (SeqSet.hpp:1533-1556) as a second sweep of the wide kernels -- seed stage of the queued reads of both halves
       // into fresh slots of half 0, the five kernels from those slots on, the extensions of the new records. One such sweep per attempt.
       q.sweep2Done = true;
-      const int *ctl0 = (const int *)(c->aqOutHost + q.pWctl), *ctlA0 = (const int *)(c->aqOutHost + q.pWctlA);
-      const int nq0 = ctl0[4], nqA = ctlA0[4];
-      if (nq0 + nqA > 0 && !ctl0[2] && !ctlA0[2]) {
-        T4Wide w, wa;
-        memcpy(&w, c->aqInHost + q.oWide, sizeof w);
-        memcpy(&wa, c->aqInHost + q.oWideA, sizeof wa);
-        const int *list0 = w.requeue, *listA = wa.requeue;
-        w.firstRead = ctl0[0]; w.firstPart = ctl0[1];
-        const int recsBefore = (int)*(const unsigned *)(c->aqOutHost + pTail + 24);
-        const int cus = c->cus > 0 ? c->cus : 1;
-        auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; };
-        const int nq = nq0 + nqA;
-        const int gParts = clampi(2 * c->wideRecentParts + 4 * nq + 4, 4, cus * 2), gReads = clampi(nq, 1, cus < 64 ? cus : 64);
-        q.lazyStage = true;
-        HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-        if (nq0 > 0) hipLaunchKernelGGL(t4k::wideSeedKernel, dim3(nq0 < cus ? nq0 : cus), dim3(512), 0, c->stream, q.base, bv, wk, qa, w, list0, nq0, 0);
-        if (nqA > 0) hipLaunchKernelGGL(t4k::wideSeedKernel, dim3(nqA < cus ? nqA : cus), dim3(512), 0, c->stream, q.base, bv, wk, qa, w, listA, nqA, 0);
-        hipLaunchKernelGGL(t4k::wideScatterKernel, dim3(clampi(8 * gParts, 16, cus * 8)), dim3(256), 0, c->stream, q.base, w);
-        hipLaunchKernelGGL((t4k::wideSortKernel<8192>), dim3(gParts), dim3(512), 0, c->stream, q.base, w);
-        hipLaunchKernelGGL(t4k::wideStatsKernel, dim3(gReads), dim3(512), 0, c->stream, q.base, w);
-        hipLaunchKernelGGL((t4k::wideChainKernel<8192, 1 << T4_WIDE_OVBITS>), dim3(gParts < cus ? gParts : cus), dim3(512), 0, c->stream, q.base, bv, wk, qa, w);
-        hipLaunchKernelGGL(t4k::wideMergeKernel, dim3(gReads), dim3(512), 0, c->stream, q.base, bv, wk, qa, w);
-        HIPCHK(c, hipGetLastError());
-        if (q.extendLater) {
-          hipLaunchKernelGGL(t4k::extendKernel, dim3(c->cus * 16), dim3(64), 0, c->stream, q.base, bv, qa, recsBefore < c->aqPoolCap ? recsBefore : c->aqPoolCap);
-          HIPCHK(c, hipGetLastError());
-        }
-        HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-        if ((r = aqLaunchEpilogue(c))) return r;
+      const int nq[2] = {ctl[T4_WC_REQUEUED], ctlA[T4_WC_REQUEUED]}, nqAll = nq[0] + nq[1];
+      if (wideClean && nqAll > 0) {
+        T4Wide w = *q.in.wide[0].stage(c);
+        const int *const lists[2] = {w.requeue, q.in.wide[1].stage(c)->requeue};
+        w.firstRead = ctl[T4_WC_READS]; w.firstPart = ctl[T4_WC_PARTS];
+        r = aqStage(c, [&] {
+          for (int half = 0; half < 2; ++half) if (nq[half] > 0) launchWideSeed(c, c->stream, w, wk, lists[half], nq[half], 0);
+          launchWide(c, c->stream, w, wk, wideGridParts(c, 2 * c->wideRecentParts + 4 * nqAll + 4), wideGridReads(c, nqAll));
+        });
+        if (r) return r;
         continue;
       }
     }
-    int overflow = *(int *)(c->aqOutHost + pTail);
-    { const int inKernel = *(int *)(c->aqOutHost + pTail + 8); if (!smallFirst && inKernel > 0) { c->aqGlobalReads += inKernel; ++c->aqGlobalLaunches; } }
-    c->aqSecFirst += tSince(q.tf0);
-    auto tg0 = tNow();
+    int overflow = tail->overflow;
+    if (!smallFirst && tail->servedGlobal > 0) { c->aqGlobalReads += tail->servedGlobal; ++c->aqGlobalLaunches; }
+    c->aqSecFirst += secondsSince(q.tf0);
+    const auto tg0 = std::chrono::steady_clock::now();
+    const AqField<int> *overflowList = &hdr.next;
     if (overflow > 0 && smallFirst) {   // reads beyond the 1024-hit tier: 8192-hit LDS tier
       T4Work w1 = wk;
-      w1.list = (const int *)(c->aqOut + pNext); w1.nList = overflow;
-      w1.nextList = (int *)(c->aqOut + pNext2); w1.nextCount = (int *)(c->aqOut + pTail + 8);
+      w1.list = hdr.next.dev(c); w1.nList = overflow;
+      w1.nextList = hdr.next2.dev(c); w1.nextCount = &hdr.tail.dev(c)->overflow2;
       if ((r = ensureScratch(c, (overflow > c->cus * 2 ? overflow : c->cus * 2) * q.threads))) return r;
       w1.dpRows = c->dpRows; w1.dpDir = c->dpDir;
-      HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-      launchTier<8192, 512, 256>(overflow, c->stream, q.base, bv, w1, qa);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-      HIPCHK(c, hipMemcpyAsync(c->aqOutHost, c->aqOut, outBytes, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      { float ms = 0; if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->aqKernelMs += ms; }
-      overflow = *(int *)(c->aqOutHost + pTail + 8);
-      wk.nextList = (int *)(c->aqOut + pNext2);
+      if ((r = aqRerun(c, [&] { launchTier<8192, 512, 256>(overflow, c->stream, q.base, q.bv, w1, q.qa); }))) return r;
+      overflow = tail->overflow2;
+      overflowList = &hdr.next2;
     }
     ++c->aqCalls; c->aqReads += n;
     if (overflow > 0 && q.tierHint) {   // remembered by the caller for the next query of these reads
-      const int *lst = (const int *)(c->aqOutHost + (wk.nextList == (int *)(c->aqOut + pNext2) ? pNext2 : pNext));
+      const int *lst = overflowList->host(c);
       for (int t = 0; t < overflow; ++t) q.tierHint[lst[t]] = 1;
     }
     if (overflow > 0) {   // reads beyond the LDS tiers: global-scratch tier
@@ -2217,70 +2282,21 @@ int aqEnd(t4_ctx *c, AqResult *res) {
       if ((r = ensureGlobalTier(c, overflow))) return r;
       if ((r = ensureScratch(c, (overflow > c->cus * 2 ? overflow : c->cus * 2) * G_THREADS))) return r;
       T4Work w2 = wk;
-      w2.list = wk.nextList; w2.nList = overflow; w2.nextList = nullptr; w2.nextCount = nullptr;
+      w2.list = overflowList->dev(c); w2.nList = overflow; w2.nextList = nullptr; w2.nextCount = nullptr;
       w2.gKeys = c->gKeys; w2.gPairs = c->gPairs; w2.gCand = c->gCand; w2.gOv = c->gOv; w2.gFin = c->gFin; w2.gOrd = c->gOrd;
       w2.gCap = G_CAP; w2.gMaxOv = G_MAXOV;
       w2.dpRows = c->dpRows; w2.dpDir = c->dpDir;
-      HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-      const int recsBefore = (int)*(const unsigned *)(c->aqOutHost + pTail + 24);
-      launchTier<0, 0, G_THREADS>(overflow, c->stream, q.base, bv, w2, qa);
-      HIPCHK(c, hipGetLastError());
-      if (q.extendLater) {
-        hipLaunchKernelGGL(t4k::extendKernel, dim3(c->cus * 16), dim3(64), 0, c->stream, q.base, bv, qa, recsBefore < c->aqPoolCap ? recsBefore : c->aqPoolCap);
-        HIPCHK(c, hipGetLastError());
-      }
-      HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-      HIPCHK(c, hipMemcpyAsync(c->aqOutHost, c->aqOut, outBytes, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      { float ms = 0; if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->aqKernelMs += ms; }
+      if ((r = aqRerun(c, [&] { launchTier<0, 0, G_THREADS>(overflow, c->stream, q.base, q.bv, w2, q.qa); }))) return r;
     }
-    c->aqSecGlobal += tSince(tg0);
-    const unsigned char *o = c->aqOutHost;
+    c->aqSecGlobal += secondsSince(tg0);
     if (q.wide) {
-      const int *ctl = (const int *)(o + q.pWctl), *ctlA = (const int *)(o + q.pWctlA);
-      const int flags = ctl[2] | ctlA[2];
-      if (flags) {   // a pool of the wide query ran out: larger pools / finer partitions, and the whole call again
-        if (q.attempt >= 12 || (flags & (1 | 32))) return fail(c, T4_ERR_UNSUPPORTED, "wide query: flags %d after %d attempts", flags, q.attempt);
-        if (flags & 2) {
-          const int need = ctl[1] > ctlA[1] ? ctl[1] : ctlA[1];
-          if (need <= c->wide.maxPart) return fail(c, T4_ERR_UNSUPPORTED, "a read of this batch needs more than %d partitions of %d k-mer hits", T4_WIDE_MAXP, c->wide.pcap);
-          if ((r = ensureWide(c, q.nWideSlots, need, 1))) return r;
-        }
-        for (int b = 0; b < 6; ++b) if (flags & (1 << b)) ++c->wideFlagCounts[b];
-        if (flags & (4 | 8)) {
-          if (q.wideSafety >= 32 * 256) return fail(c, T4_ERR_UNSUPPORTED, "wide query: a contig range of one contig overflows a partition");
-          q.wideSafety *= 2;
-          // keys: the partitions are quantiles of a SAMPLE of the hits' contigs; when a sample misjudged one, the next calls (the same
-          // reads again, mostly) are planned less full as well. Overlaps of a partition: one read's matter (hundreds of short chains in
-          // one contig range) -- finer partitions for this call only.
-          if (flags & 4) { c->wideSafetyKeep = q.wideSafety < 128 ? q.wideSafety : 128; c->wideCallsSinceRepeat = 0; }
-        }
-        if (flags & 16) { if ((r = ensureWide(c, q.nWideSlots, 1, ctl[3] > ctlA[3] ? ctl[3] : ctlA[3]))) return r; }
-        ++c->wideRetries; ++q.attempt;
-        if ((r = aqLaunch(c))) return r;
+      if (const int flags = ctl[T4_WC_FLAGS] | ctlA[T4_WC_FLAGS]) {   // a pool of the wide query ran out: the whole call again
+        if ((r = aqWideGrow(c, flags)) || (r = aqRepeat(c))) return r;
         continue;
       }
-      // (slots of first passes that found nothing were retired, T4WidePlan::read < 0: their partitions and dependency records are not counted)
-      int retiredParts[2] = {0, 0}, retiredGroups = 0;
-      if (ctl[4] + ctlA[4] > 0) {
-        for (int hlf = 0; hlf < 2; ++hlf) {
-          const T4WidePlan *pl = (const T4WidePlan *)(o + (hlf ? q.pWplanA : q.pWplan));
-          const int *st = (const int *)(o + (hlf ? q.pWstatA : q.pWstat));
-          const int nw = (hlf ? ctlA[0] : ctl[0]) < q.nWideSlots ? (hlf ? ctlA[0] : ctl[0]) : q.nWideSlots;
-          for (int w2 = 0; w2 < nw; ++w2) if (pl[w2].read < 0) { retiredParts[hlf] += pl[w2].P; retiredGroups += st[(size_t)w2 * T4_WIDE_STAT + WS_GROUPS]; }
-        }
-      }
-      c->wideReads += ctl[0] + ctlA[0] - ctl[4] - ctlA[4]; c->wideParts += ctl[1] + ctlA[1] - retiredParts[0] - retiredParts[1]; c->wideGroups += ctl[3] + ctlA[3] - retiredGroups;
-      ++c->wideCalls; if (ctl[0] > 0) ++c->wideCallsDeferred; if (ctlA[0] > 0) ++c->wideCallsDirect;
-      if (ctl[0] + ctlA[0] > 0 && ++c->wideCallsSinceRepeat >= 2048 && c->wideSafetyKeep > 32) { c->wideSafetyKeep /= 2; c->wideCallsSinceRepeat = 0; }
-      { const int parts = ctl[1] - retiredParts[0]; c->wideRecentParts = parts > c->wideRecentParts ? parts : (c->wideRecentParts * 7 + parts) / 8; }
-      if (q.tierHint) {   // remembered by the caller: these reads start on the second stream the next time they are queried
-        const T4WidePlan *plans[2] = {(const T4WidePlan *)(o + q.pWplan), (const T4WidePlan *)(o + q.pWplanA)};
-        const int cnt[2] = {ctl[0] < q.nWideSlots ? ctl[0] : q.nWideSlots, ctlA[0] < q.nWideSlots ? ctlA[0] : q.nWideSlots};
-        for (int hlf = 0; hlf < 2; ++hlf) for (int w2 = 0; w2 < cnt[hlf]; ++w2) if (plans[hlf][w2].read >= 0 && plans[hlf][w2].read < n) q.tierHint[plans[hlf][w2].read] = 1;
-      }
+      aqWideAccount(c);
     }
-    const int *status = (const int *)(o + q.pSta);
+    const int *status = hdr.status.host(c);
     bool poolFull = false;
     for (int i = 0; i < n; ++i) {
       if (status[i] == 3) poolFull = true;
@@ -2288,34 +2304,29 @@ int aqEnd(t4_ctx *c, AqResult *res) {
       else if (status[i]) return fail(c, T4_ERR_UNSUPPORTED, "read %d exceeds the engine limits (status %d: %s)", i, status[i],
                                       status[i] == 2 ? "more k-mer hits or overlaps than the global tier holds" : "a posting list beyond 10000 entries, or gap DP or contig count beyond scratch");
     }
-    if (*(const unsigned *)(o + pTail + 28)) return fail(c, T4_ERR_UNSUPPORTED, "an overhang alignment of this batch exceeds the extension kernel's direction buffer");
-    if (q.wantCands && *(const int *)(o + pTail + 36)) {   // more candidate records than their pool holds: a larger pool, and the whole call again
+    if (tail->dirOverflow) return fail(c, T4_ERR_UNSUPPORTED, "an overhang alignment of this batch exceeds the extension kernel's direction buffer");
+    if (q.wantCands && tail->candOverflow) {   // more candidate records than their pool holds: a larger pool, and the whole call again
       if (q.attempt >= 12) return fail(c, T4_ERR_UNSUPPORTED, "candidate pool of %d records overflows", c->candCap);
-      const unsigned want = *(const unsigned *)(o + pTail + 32);
-      (void)hipHostFree(c->candPool);
-      c->candPool = nullptr; c->candPoolDev = nullptr; ++c->candGrows;
-      while ((unsigned)c->candCap < want && c->candCap < (1 << 29)) c->candCap *= 2;
+      while ((unsigned)c->candCap < tail->candCursor && c->candCap < (1 << 29)) c->candCap *= 2;
       c->candCap *= 2;
-      ++q.attempt;
-      if ((r = aqLaunch(c))) return r;
+      c->candPoolDev = nullptr; ++c->candGrows;
+      if ((r = aqRepeat(c, &c->candPool))) return r;
       continue;
     }
     if (poolFull) {   // more result records than the pool holds: a larger pool, and the whole call again
       if (q.attempt >= 8) return fail(c, T4_ERR_UNSUPPORTED, "result pool of %d records overflows", c->aqPoolCap);
-      (void)hipHostFree(c->aqPool);
-      c->aqPool = nullptr; c->aqPoolDev = nullptr; c->aqPoolCap *= 4; ++c->aqPoolGrows;
-      ++q.attempt;
-      if ((r = aqLaunch(c))) return r;
+      c->aqPoolDev = nullptr; c->aqPoolCap *= 4; ++c->aqPoolGrows;
+      if ((r = aqRepeat(c, &c->aqPool))) return r;
       continue;
     }
     const size_t rec = (size_t)c->aqPoolCap;
-    c->aqRecords += *(const unsigned *)(o + pTail + 24);
-    c->aqDeferredReads += *(const unsigned *)(o + pTail + 40);
-    if (q.wantCands) c->candRecords += *(const unsigned *)(o + pTail + 32);
-    c->aqHits += (int64_t) * (const unsigned long long *)(o + pTail + 16);
-    c->aqLastTicks = (const int32_t *)(o + q.pTick); c->aqLastN = n;
-    c->aqLastStable = (const int32_t *)(o + q.pStab);
-    res->counts = (const int32_t *)(o + q.pCnt); res->base = (const int32_t *)(o + q.pBase);
+    c->aqRecords += tail->poolCursor;
+    c->aqDeferredReads += tail->deferred;
+    if (q.wantCands) c->candRecords += tail->candCursor;
+    c->aqHits += (int64_t)tail->hits;
+    c->aqLastTicks = hdr.ticks.host(c); c->aqLastN = n;
+    c->aqLastStable = hdr.stable.host(c);
+    res->counts = hdr.counts.host(c); res->base = hdr.outBase.host(c);
     res->ov = (const t4_overlap *)c->aqPool; res->ext = res->ov + rec; res->ret = (const int32_t *)(res->ext + rec);
     return T4_OK;
   }
@@ -2389,8 +2400,8 @@ int assignWidePass2(t4_index *ix, t4_batch *b, const std::vector<int64_t> &todo,
     const AqCall &q = c->aq;
     const size_t rec = (size_t)c->aqPoolCap;
     const T4OverlapOut *ov = (const T4OverlapOut *)c->aqPoolDev;
-    launch(t4k::assignPickKernel, m, T4_PICK_THREADS, c->stream, m, (const int *)(c->aqOut + q.pCnt), (const int *)(c->aqOut + q.pBase),
-           (const int *)(c->aqIn + q.oLen), ov, ov + rec, (const int *)(ov + 2 * rec), c->aqExtAux, c->aqPoolCap, dRet, dOut);
+    launch(t4k::assignPickKernel, m, T4_PICK_THREADS, c->stream, m, q.hdr.counts.dev(c), q.hdr.outBase.dev(c), q.in.len.dev(c), ov,
+           ov + rec, (const int *)(ov + 2 * rec), c->aqExtAux, c->aqPoolCap, dRet, dOut);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(hRet.data(), dRet, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(hOut.data(), dOut, sizeof(t4_overlap) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
@@ -2438,22 +2449,15 @@ int t4_add_query_groups(t4_ctx *c, int i, const t4_grp **groups, int *n, int *hu
   if (!c || !groups || !n) return T4_ERR_ARG;
   const AqCall &q = c->aq;
   if (!q.wide || !c->aqOutHost) return 0;
-  const unsigned char *o = c->aqOutHost;
-  for (int half = 0; half < 2; ++half) {
-    const int *ctl = (const int *)(o + (half ? q.pWctlA : q.pWctl));
-    const T4WidePlan *plan = (const T4WidePlan *)(o + (half ? q.pWplanA : q.pWplan));
-    const int *stat = (const int *)(o + (half ? q.pWstatA : q.pWstat));
-    const int nw = ctl[0] < q.nWideSlots ? ctl[0] : q.nWideSlots;
-    for (int w = 0; w < nw; ++w) {
-      if (plan[w].read != i) continue;
-      *groups = (const t4_grp *)c->grpPoolHost + (half ? (size_t)c->wide.grpCap : 0) + plan[w].grpBase;
-      *n = stat[(size_t)w * T4_WIDE_STAT + WS_GROUPS];
-      if (huge) *huge = plan[w].huge;
-      if (n4) *n4 = stat[(size_t)w * T4_WIDE_STAT + WS_N4];
-      return 1;
-    }
-  }
-  return 0;
+  const WideSlot at = findWideSlot(c, i);
+  if (at.half < 0) return 0;
+  const T4WidePlan &plan = q.hdr.wide[at.half].plan.host(c)[at.slot];
+  const int *st = q.hdr.wide[at.half].stat.host(c) + (size_t)at.slot * T4_WIDE_STAT;
+  *groups = (const t4_grp *)c->grpPoolHost + (at.half ? (size_t)c->wide.grpCap : 0) + plan.grpBase;
+  *n = st[WS_GROUPS];
+  if (huge) *huge = plan.huge;
+  if (n4) *n4 = st[WS_N4];
+  return 1;
 }
 
 // The head of read i of the last finished AddRead query call on this ctx, when the wide query served it and one of its lists holds
@@ -2465,23 +2469,13 @@ int t4_add_query_head(t4_ctx *c, int i, int *m, const uint32_t **bits, int *ror)
   if (!c || !m || !bits || !ror) return T4_ERR_ARG;
   const AqCall &q = c->aq;
   if (!q.wide || !c->aqOutHost || !c->headBitsHost) return 0;
-  const unsigned char *o = c->aqOutHost;
-  for (int half = 0; half < 2; ++half) {
-    const int *ctl = (const int *)(o + (half ? q.pWctlA : q.pWctl));
-    const T4WidePlan *plan = (const T4WidePlan *)(o + (half ? q.pWplanA : q.pWplan));
-    const int *stat = (const int *)(o + (half ? q.pWstatA : q.pWstat));
-    const int nw = ctl[0] < q.nWideSlots ? ctl[0] : q.nWideSlots;
-    for (int w = 0; w < nw; ++w) {
-      if (plan[w].read != i) continue;
-      if (!plan[w].huge) return 0;
-      const int *st = stat + (size_t)w * T4_WIDE_STAT;
-      *m = st[WS_M];
-      *ror = (st[WS_ROR] ? 1 : 0) | (st[WS_ROR + 1] ? 2 : 0);
-      *bits = c->headBitsHost + ((half ? (size_t)c->wide.maxReads : 0) + (size_t)w) * ((c->wide.pcap + 31) / 32);
-      return 1;
-    }
-  }
-  return 0;
+  const WideSlot at = findWideSlot(c, i);
+  if (at.half < 0 || !q.hdr.wide[at.half].plan.host(c)[at.slot].huge) return 0;
+  const int *st = q.hdr.wide[at.half].stat.host(c) + (size_t)at.slot * T4_WIDE_STAT;
+  *m = st[WS_M];
+  *ror = (st[WS_ROR] ? 1 : 0) | (st[WS_ROR + 1] ? 2 : 0);
+  *bits = c->headBitsHost + ((at.half ? (size_t)c->wide.maxReads : 0) + (size_t)at.slot) * wideHeadWords(c->wide);
+  return 1;
 }
 
 // Arms the restricted re-queries of the NEXT t4_add_query_pool_begin2 call on this ctx (which must have n reads and an only_seq)
@@ -2512,7 +2506,7 @@ int t4_add_query_arm_long_lists(t4_ctx *c, int n, const int32_t *arm, const int3
 int t4_add_query_last_long_lists(t4_ctx *c, const int32_t **info, int *n) {
   if (!c || !info) return T4_ERR_ARG;
   const AqCall &q = c->aq;
-  *info = (q.hasArm && c->aqOutHost) ? (const int32_t *)(c->aqOutHost + q.pRor) : nullptr;
+  *info = (q.hasArm && c->aqOutHost) ? q.hdr.rorInfo.host(c) : nullptr;
   if (n) *n = q.n;
   return T4_OK;
 }
@@ -2522,9 +2516,9 @@ int t4_add_query_last_long_lists(t4_ctx *c, const int32_t **info, int *n) {
 int t4_add_query_last_aux(t4_ctx *c, const int32_t **aux, const int32_t **n4, const int32_t **status, int *n) {
   if (!c || !c->aqOutHost) return T4_ERR_ARG;
   const AqCall &q = c->aq;
-  if (aux) *aux = (const int32_t *)(c->aqOutHost + q.pAux);
-  if (n4) *n4 = (const int32_t *)(c->aqOutHost + q.pN4);
-  if (status) *status = (const int32_t *)(c->aqOutHost + q.pSta);
+  if (aux) *aux = q.hdr.aux.host(c);
+  if (n4) *n4 = q.hdr.n4.host(c);
+  if (status) *status = q.hdr.status.host(c);
   if (n) *n = q.n;
   return T4_OK;
 }
@@ -2610,9 +2604,9 @@ int t4_add_query_last_cands(t4_ctx *c, const t4_cand **pool, const int32_t **bas
   const AqCall &q = c->aq;
   static_assert(sizeof(t4_cand) == sizeof(T4Cand) && sizeof(T4Cand) == 24 && T4_QUERY_STATS == T4_QSTATS, "candidate record layout");
   if (pool) *pool = q.wantCands ? (const t4_cand *)c->candPool : nullptr;
-  if (base) *base = (const int32_t *)(c->aqOutHost + q.pCb);
-  if (cnt) *cnt = q.wantCands ? (const int32_t *)(c->aqOutHost + q.pCc) : nullptr;
-  if (stats8) *stats8 = (const int32_t *)(c->aqOutHost + q.pS8);
+  if (base) *base = q.hdr.candBase.host(c);
+  if (cnt) *cnt = q.wantCands ? q.hdr.candCnt.host(c) : nullptr;
+  if (stats8) *stats8 = q.hdr.stats8.host(c);
   if (n) *n = q.n;
   return T4_OK;
 }

@@ -1,5 +1,6 @@
 // trust4_amd/csrc/t4_device.h -- POD views shared by the host side (t4_api.hip) and the kernels.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #define T4_MAXL 384          // longest read the kernels take (150 bp mates merge to <= ~290 bp)
@@ -98,13 +99,24 @@ struct T4WidePlan { int pBase, P, pass /* 1: the first pass of a skipRepeats que
                     int huge /* a list beyond 10000 postings (never in a first pass, never for a barcoded read: its hits all count repeats = 1) */, read /* -1 - read: a first pass that found nothing, queued again */, grpBase;
                     int barcode /* -1, or the only contig barcode whose postings are hits (an index that is not keyed by barcode) */; };
 #define T4_WIDE_STAT 24      // ints per read: see wideStatsKernel
+enum T4WideCtl {             // words of T4Wide::ctl
+  T4_WC_READS = 0,           // read slots taken
+  T4_WC_PARTS = 1,           // partitions taken
+  T4_WC_FLAGS = 2,           // T4WideFlag bits: a pool ran out, the kernels behind return at once and the host repeats the call
+  T4_WC_GROUPS = 3,          // group pool cursor
+  T4_WC_REQUEUED = 4,        // first passes that ended without a raw overlap: their reads wait in `requeue` for a second sweep as plain passes
+  T4_WC_WORDS = 8            // (32 bytes in the header blob)
+};
+enum T4WideFlag {            // what ran out
+  T4_WF_READS = 1, T4_WF_PARTS = 2, T4_WF_KEYS = 4 /* keys of a partition */, T4_WF_OVERLAPS = 8 /* overlaps of a partition */, T4_WF_GROUPS = 16 /* group pool */,
+  T4_WF_INTERNAL = 32        // (cannot happen: wideStatsKernel)
+};
 struct T4Wide {
   int enabled;
   int maxReads, maxPart, pcap, maxOvPart, safetyNum /* partitions are planned for pcap * 16 / safetyNum hits */, maxPartPerRead;
   int minHits;               // a read goes wide when its seed stage emits more hits than this (or meets a list beyond 10000 postings, or outgrows the global-scratch tier)
   int firstRead, firstPart;  // the kernels behind the seed stage start at this read slot / partition (second sweep: the slots before are done)
-  int *ctl;                  // [0] reads, [1] partitions, [2] overflow flags (1 reads, 2 partitions, 4 keys of a partition, 8 overlaps of a partition, 16 group pool), [3] group pool cursor,
-                             // [4] first passes that ended without a raw overlap: their reads wait in `requeue` for a second sweep as plain passes
+  int *ctl;                  // control block of this half, T4_WC_WORDS ints indexed by T4WideCtl
   int *requeue;              // [maxReads]
   T4WidePlan *plan;          // [maxReads]
   uint2 *seed;               // [maxReads][2 * T4_MAXL]: (start, emitted postings) of every k-mer position, forward strand first
@@ -261,6 +273,36 @@ struct T4QueryArgs {
   const T4IndexView *views;
   const int *viewOf;
 };
+
+// Tail of the header blob of an AddRead query call (t4_api.hip: AqCall): the single words of the call. The host reads them by name;
+// the kernels reach them through the pointers of T4Work (nextCount, hitCounter), T4QueryArgs (poolCursor) and T4CandArgs
+// (candCursor, candOverflow) and, to spare T4QueryArgs and T4Work a pointer each, by the indices below off those pointers.
+struct T4AqTail {
+  int overflow;              // T4Work::nextCount of the call's first launch: reads that outgrew its tier (listed in the header's next1)
+  int pad0;
+  union {
+    int overflow2;           // per-cell images (small tier first): nextCount of the 8192-hit rerun (listed in next2)
+    int servedGlobal;        // one big set: reads the first launch went on with in its workgroup's global scratch (statistics)
+  };
+  int pad1;
+  unsigned long long hits;   // T4Work::hitCounter
+  unsigned poolCursor;       // T4QueryArgs::poolCursor: result records taken from the pool
+  unsigned dirOverflow;      // extendKernel: an overhang alignment beyond the direction buffer
+  unsigned candCursor;       // T4CandArgs::candCursor
+  int candOverflow;          // T4CandArgs::candOverflow
+  unsigned deferred;         // reads whose ExtendOverlap calls were left to extendKernel (statistics)
+  unsigned pad2;
+};
+enum {
+  T4_NEXTCOUNT_SERVED_GLOBAL = 2,   // ints behind T4Work::nextCount
+  T4_POOLCURSOR_DIR_OVERFLOW = 1,   // words behind T4QueryArgs::poolCursor
+  T4_POOLCURSOR_DEFERRED = 4
+};
+static_assert(sizeof(T4AqTail) == 48 && offsetof(T4AqTail, overflow) == 0 && offsetof(T4AqTail, hits) == 16, "tail of the AddRead header blob");
+static_assert(offsetof(T4AqTail, servedGlobal) == offsetof(T4AqTail, overflow) + sizeof(int) * T4_NEXTCOUNT_SERVED_GLOBAL && offsetof(T4AqTail, overflow2) == offsetof(T4AqTail, servedGlobal), "word behind nextCount");
+static_assert(offsetof(T4AqTail, dirOverflow) == offsetof(T4AqTail, poolCursor) + sizeof(unsigned) * T4_POOLCURSOR_DIR_OVERFLOW, "word behind poolCursor");
+static_assert(offsetof(T4AqTail, deferred) == offsetof(T4AqTail, poolCursor) + sizeof(unsigned) * T4_POOLCURSOR_DEFERRED, "word behind poolCursor");
+static_assert(offsetof(T4AqTail, poolCursor) == 24 && offsetof(T4AqTail, candCursor) == 32 && offsetof(T4AqTail, candOverflow) == 36, "tail of the AddRead header blob");
 
 struct T4BytePatch { unsigned char *dst; unsigned long long val; };   // one posWeight predicate byte of a resident image
 struct T4CopyDesc { unsigned long long srcOff; unsigned char *dst; unsigned long long bytes; };  // scatter of staged set images

@@ -3753,7 +3753,7 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
       for (int i = lane; i < n; i += NT) qa.recRead[base + i] = defer ? (int)r : -1;
       if (defer) {
         for (int i = lane; i < n; i += NT) storeOverlap(qa.outDev + base + i, wm.fin[i]);
-        if (lane == 0) { qa.counts[r] = ret; atomicAdd(qa.poolCursor + 4, 1u); }   // statistics: reads deferred (t4_add_query_defer_stats)
+        if (lane == 0) { qa.counts[r] = ret; atomicAdd(qa.poolCursor + T4_POOLCURSOR_DEFERRED, 1u); }   // statistics: reads deferred (t4_add_query_defer_stats)
         return true;
       }
     }
@@ -4111,7 +4111,7 @@ void queryKernel(T4IndexView ixArg, T4BatchView bvArg, T4Work wkArg, T4QueryArgs
       }
       __syncthreads();
       done = processRead<1>(ix, bv, wk, qa, wg, &s_ws, r, sc);
-      if (tid() == 0 && done && wk.nextCount) atomicAdd(wk.nextCount + 2, 1);   // statistics: reads served this way
+      if (tid() == 0 && done && wk.nextCount) atomicAdd(wk.nextCount + T4_NEXTCOUNT_SERVED_GLOBAL, 1);   // statistics: reads served this way
     }
     if (tid() == 0) {
 #ifdef __HIPCC__
@@ -4196,7 +4196,7 @@ __global__ __launch_bounds__(64) void extendKernel(T4IndexView ix, T4BatchView b
         qa.ret[i0 + lane] = e.ret;
         if (qa.cs && qa.cs->extAux) qa.cs->extAux[i0 + lane] = e.simFail ? 0 : e.den;
       }
-      if (lane == 0 && s_ws.unsupported) qa.poolCursor[1] = 1u;   // an overhang beyond the direction buffer (reads of more than 600 bases)
+      if (lane == 0 && s_ws.unsupported) qa.poolCursor[T4_POOLCURSOR_DIR_OVERFLOW] = 1u;   // an overhang beyond the direction buffer (reads of more than 600 bases)
       __syncthreads();
       i0 = i1;
     }

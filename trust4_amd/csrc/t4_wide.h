@@ -43,8 +43,8 @@ __device__ T4_NI void wideDeferRead(const T4IndexView &ix, WaveMem &wm, WaveStat
   if (barcode == -1) for (int q = lane; q < 2 * nk; q += NT) if (posPref[q + 1] - posPref[q] > 10000u) huge = 1;
   huge = blockSum(huge, ws->red) != 0;
   if (lane == 0) {
-    int slot = atomicAdd(&wd.ctl[0], 1), pBase = 0, P = 0;
-    if (slot >= wd.maxReads) { atomicOr(&wd.ctl[2], 1); slot = -1; }
+    int slot = atomicAdd(&wd.ctl[T4_WC_READS], 1), pBase = 0, P = 0;
+    if (slot >= wd.maxReads) { atomicOr(&wd.ctl[T4_WC_FLAGS], (int)T4_WF_READS); slot = -1; }
     else {
       const long long per = 16LL * wd.pcap;
       long long want = ((long long)H * wd.safetyNum + per - 1) / per;
@@ -52,10 +52,10 @@ __device__ T4_NI void wideDeferRead(const T4IndexView &ix, WaveMem &wm, WaveStat
       if (want < 1) want = 1;
       if (want > nseq) want = nseq;
       P = (int)want;
-      if (P > wd.maxPartPerRead) { atomicOr(&wd.ctl[2], 2); P = 0; }
+      if (P > wd.maxPartPerRead) { atomicOr(&wd.ctl[T4_WC_FLAGS], (int)T4_WF_PARTS); P = 0; }
       else {
-        pBase = atomicAdd(&wd.ctl[1], P);
-        if (pBase + P > wd.maxPart) { atomicOr(&wd.ctl[2], 2); P = 0; }
+        pBase = atomicAdd(&wd.ctl[T4_WC_PARTS], P);
+        if (pBase + P > wd.maxPart) { atomicOr(&wd.ctl[T4_WC_FLAGS], (int)T4_WF_PARTS); P = 0; }
       }
       T4WidePlan pl;
       pl.pBase = pBase; pl.P = P; pl.pass = pass == 1 ? 1 : 0; pl.barcode = barcode; pl.nk = nk; pl.H = (unsigned)H; pl.huge = huge; pl.read = (int)r; pl.grpBase = 0;
@@ -138,8 +138,8 @@ __global__ __launch_bounds__(512) void wideSeedKernel(T4IndexView ixArg, T4Batch
   }
 }
 
-__device__ __forceinline__ int wideReads(const T4Wide &wd) { const int n = wd.ctl[0]; return n < wd.maxReads ? n : wd.maxReads; }
-__device__ __forceinline__ int wideParts(const T4Wide &wd) { const int n = wd.ctl[1]; return n < wd.maxPart ? n : wd.maxPart; }
+__device__ __forceinline__ int wideReads(const T4Wide &wd) { const int n = wd.ctl[T4_WC_READS]; return n < wd.maxReads ? n : wd.maxReads; }
+__device__ __forceinline__ int wideParts(const T4Wide &wd) { const int n = wd.ctl[T4_WC_PARTS]; return n < wd.maxPart ? n : wd.maxPart; }
 
 // postings -> keys -> partitions. A work item is a chunk of 1024 postings of one deferred read; the items of all reads form one list
 // that the blocks stride over (a round's latency is what counts: every thread issues its four gathers before the first of the
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void wideScatterKernel(T4IndexView ix, T4Wide 
   __shared__ unsigned s_start[T4_WIDE_SEEDS];
   __shared__ int s_bound[T4_WIDE_MAXP + 1];
   __shared__ int s_item[2];
-  if (wd.ctl[2]) return;
+  if (wd.ctl[T4_WC_FLAGS]) return;
   const int nR = wideReads(wd), lane = threadIdx.x, NT = blockDim.x;
   int loaded = -1;
   for (unsigned item = blockIdx.x;; item += gridDim.x) {
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void wideScatterKernel(T4IndexView ix, T4Wide 
         if (has && part[t] == p0) {
           const unsigned at = base + (unsigned)__popcll(same & ((1ull << wl) - 1ull));
           if (at < (unsigned)wd.pcap) wd.pKeys[(size_t)(pl.pBase + p0) * wd.pcap + at] = key[t];
-          else atomicOr(&wd.ctl[2], 4);
+          else atomicOr(&wd.ctl[T4_WC_FLAGS], (int)T4_WF_KEYS);
         }
         todo &= ~same;
       }
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(512) void wideSortKernel(T4IndexView ix, T4Wide wd)
   __shared__ unsigned s_gs[PCAP + 1];
   __shared__ unsigned s_cnt[T4_WIDE_SEEDS];
   __shared__ int s_red[16];
-  if (wd.ctl[2]) return;
+  if (wd.ctl[T4_WC_FLAGS]) return;
   const int nPart = wideParts(wd), lane = threadIdx.x, NT = blockDim.x;
   for (int pg = wd.firstPart + blockIdx.x; pg < nPart; pg += gridDim.x) {
     const int w = wd.pRead[pg];
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(512) void wideStatsKernel(T4IndexView ix, T4Wide wd
   __shared__ unsigned s_cum[8192 + 1];
   __shared__ unsigned long long s_blk[4096];
   __shared__ unsigned s_cnt[T4_WIDE_SEEDS];
-  if (wd.ctl[2]) return;
+  if (wd.ctl[T4_WC_FLAGS]) return;
   const int nR = wideReads(wd), lane = threadIdx.x, NT = blockDim.x;
   for (int w = wd.firstRead + blockIdx.x; w < nR; w += gridDim.x) {
     T4WidePlan pl = wd.plan[w];
@@ -326,8 +326,8 @@ __global__ __launch_bounds__(512) void wideStatsKernel(T4IndexView ix, T4Wide wd
     if (lane == 0) {
       s_off[2 * P] = G;
       for (int t = 0; t < 16; ++t) s_acc[t] = 0;
-      const int base = atomicAdd(&wd.ctl[3], G);
-      if (base + G > wd.grpCap) atomicOr(&wd.ctl[2], 16);
+      const int base = atomicAdd(&wd.ctl[T4_WC_GROUPS], G);
+      if (base + G > wd.grpCap) atomicOr(&wd.ctl[T4_WC_FLAGS], (int)T4_WF_GROUPS);
       wd.plan[w].grpBase = base;
     }
     __syncthreads();
@@ -441,7 +441,7 @@ __global__ __launch_bounds__(512) void wideStatsKernel(T4IndexView ix, T4Wide wd
       cum += tot;
     }
     __syncthreads();
-    if (T > 8192 || cum > 2 * wd.pcap) { if (lane == 0) atomicOr(&wd.ctl[2], 32); continue; }   // (cannot happen: cum < M + pcap, T <= cum)
+    if (T > 8192 || cum > 2 * wd.pcap) { if (lane == 0) atomicOr(&wd.ctl[T4_WC_FLAGS], (int)T4_WF_INTERNAL); continue; }   // (cannot happen: cum < M + pcap, T <= cum)
     unsigned long long *tmp = wd.sortTmp + (size_t)w * 2 * wd.pcap;
     for (int t = lane; t < T; t += NT) {
       int pg, gi;
@@ -499,7 +499,7 @@ __global__ __launch_bounds__(512) void wideChainKernel(T4IndexView ixArg, T4Batc
   __shared__ T4Work s_wk;
   __shared__ T4QueryArgs s_qa;
   __shared__ WaveMem s_wm;
-  if (wd.ctl[2]) return;
+  if (wd.ctl[T4_WC_FLAGS]) return;
   if (threadIdx.x == 0) {
     s_ix = ixArg; s_bv = bvArg; s_wk = wkArg; s_qa = qaArg;
     WaveMem &m = s_wm;
@@ -629,11 +629,11 @@ __global__ __launch_bounds__(512) void wideChainKernel(T4IndexView ixArg, T4Batc
     chainRunsRows(ix, wm, ws, nCand, ix.hitLenRequired);
     __syncthreads();
     int overlapCnt = ws->ovCount;
-    if (ws->overflow || overlapCnt > MAXOV) { if (lane == 0) atomicOr(&wd.ctl[2], 8); continue; }
+    if (ws->overflow || overlapCnt > MAXOV) { if (lane == 0) atomicOr(&wd.ctl[T4_WC_FLAGS], (int)T4_WF_OVERLAPS); continue; }
     for (int i = lane; i < overlapCnt; i += NT) s_ord[i] = (unsigned short)i;
     __syncthreads();
     // (3) gap alignments of every overlap of both strands (the strand of the read's best overlap is known to the merge only)
-    if (!scoreOverlaps<true>(ix, wm, ws, overlapCnt, sc)) { if (lane == 0) atomicOr(&wd.ctl[2], 8); continue; }
+    if (!scoreOverlaps<true>(ix, wm, ws, overlapCnt, sc)) { if (lane == 0) atomicOr(&wd.ctl[T4_WC_FLAGS], (int)T4_WF_OVERLAPS); continue; }
     __syncthreads();
     OvRec *dst = (OvRec *)wd.pRec + (size_t)pg * wd.maxOvPart;
     for (int i = lane; i < overlapCnt; i += NT) dst[i] = s_ov[i];
@@ -654,7 +654,7 @@ __global__ __launch_bounds__(512) void wideMergeKernel(T4IndexView ix, T4BatchVi
   __shared__ int s_off[T4_WIDE_MAXP + 1];
   __shared__ int s_red[16];
   __shared__ int s_best;
-  if (wd.ctl[2]) return;
+  if (wd.ctl[T4_WC_FLAGS]) return;
   const int nR = wideReads(wd), lane = threadIdx.x, NT = blockDim.x;
   for (int w = wd.firstRead + blockIdx.x; w < nR; w += gridDim.x) {
     const T4WidePlan pl = wd.plan[w];
@@ -678,7 +678,7 @@ __global__ __launch_bounds__(512) void wideMergeKernel(T4IndexView ix, T4BatchVi
     if (N == 0 && pl.pass == 1) {
       // a first pass without a raw overlap (the count of GetOverlapsFromHits, before sort and filters: SeqSet.hpp:1526-1530): the read
       // runs the plain pass next -- queued for the host's second sweep, this slot retired
-      if (lane == 0) { const int at = atomicAdd(&wd.ctl[4], 1); if (at < wd.maxReads) wd.requeue[at] = (int)r; wd.plan[w].read = -1 - (int)r; }   // (at most one entry per slot)
+      if (lane == 0) { const int at = atomicAdd(&wd.ctl[T4_WC_REQUEUED], 1); if (at < wd.maxReads) wd.requeue[at] = (int)r; wd.plan[w].read = -1 - (int)r; }   // (at most one entry per slot)
       continue;
     }
     const int *st = wd.stat + (size_t)w * T4_WIDE_STAT;
