@@ -149,6 +149,13 @@ long long hipemu_malloc_calls(void);          // hipMalloc calls so far
 void hipemu_fail_malloc(long long nth);       // the nth hipMalloc from now fails, once (nth <= 0: none does)
 int hipemu_malloc_enter(void);                // (hipMalloc: counts the call; non-zero when this one is to fail)
 void hipemu_live_add(int d);
+// ... and of pinned host memory and events, for the tests of the long-lived handles:
+long long hipemu_live_host_blocks(void);      // hipHostMalloc blocks not yet given to hipHostFree
+void hipemu_fail_host_malloc(long long nth);  // the nth hipHostMalloc from now fails, once (nth <= 0: none does)
+long long hipemu_live_events(void);           // hipEventCreate events not yet given to hipEventDestroy
+int hipemu_host_malloc_enter(void);           // (hipHostMalloc: counts the call; non-zero when this one is to fail)
+void hipemu_live_host_add(int d);
+void hipemu_live_event_add(int d);
 }
 template <class T> static inline hipError_t hipMalloc(T **p, size_t n) {
   *p = hipemu_malloc_enter() ? nullptr : (T *)calloc(1, n ? n : 1);
@@ -156,8 +163,12 @@ template <class T> static inline hipError_t hipMalloc(T **p, size_t n) {
   return *p ? hipSuccess : hipErrorUnknown;
 }
 static inline hipError_t hipFree(void *p) { if (p) hipemu_live_add(-1); free(p); return hipSuccess; }
-template <class T> static inline hipError_t hipHostMalloc(T **p, size_t n, unsigned = 0) { *p = (T *)calloc(1, n ? n : 1); return hipSuccess; }
-static inline hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
+template <class T> static inline hipError_t hipHostMalloc(T **p, size_t n, unsigned = 0) {
+  *p = hipemu_host_malloc_enter() ? nullptr : (T *)calloc(1, n ? n : 1);
+  if (*p) hipemu_live_host_add(1);
+  return *p ? hipSuccess : hipErrorUnknown;
+}
+static inline hipError_t hipHostFree(void *p) { if (p) hipemu_live_host_add(-1); free(p); return hipSuccess; }
 static inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t = 0) { memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemset(void *d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
@@ -171,8 +182,8 @@ static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 static inline hipError_t hipGetLastError() { return hipSuccess; }
 static inline hipError_t hipPeekAtLastError() { return hipSuccess; }
 static inline const char *hipGetErrorString(hipError_t) { return "hipemu"; }
-static inline hipError_t hipEventCreate(hipEvent_t *e) { *e = new hipemu_event; return hipSuccess; }
-static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+static inline hipError_t hipEventCreate(hipEvent_t *e) { *e = new hipemu_event; hipemu_live_event_add(1); return hipSuccess; }
+static inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) hipemu_live_event_add(-1); delete e; return hipSuccess; }
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t = 0) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
 static inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 static inline hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }   /* launches run to completion at once */

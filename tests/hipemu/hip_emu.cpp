@@ -20,6 +20,19 @@ int hipemu_malloc_enter(void) {
 }
 void hipemu_live_add(int d) { live_blocks += d; }
 }
+// ... of hipHostMalloc / hipHostFree and hipEventCreate / hipEventDestroy
+static std::atomic<long long> live_host_blocks(0), host_malloc_calls(0), host_fail_at(0), live_events(0);
+extern "C" {
+long long hipemu_live_host_blocks(void) { return live_host_blocks.load(); }
+void hipemu_fail_host_malloc(long long nth) { host_fail_at = nth > 0 ? host_malloc_calls.load() + nth : 0; }
+long long hipemu_live_events(void) { return live_events.load(); }
+int hipemu_host_malloc_enter(void) {
+  long long want = host_malloc_calls.fetch_add(1) + 1;
+  return host_fail_at.compare_exchange_strong(want, 0) ? 1 : 0;
+}
+void hipemu_live_host_add(int d) { live_host_blocks += d; }
+void hipemu_live_event_add(int d) { live_events += d; }
+}
 
 namespace hipemu {
 // Every host worker thread emulates whole workgroups on its own: all scheduler state is thread-local, workgroups of one

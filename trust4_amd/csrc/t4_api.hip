@@ -62,6 +62,99 @@ struct HostSeq {
 }  // namespace
 
 struct t4_ctx;
+static int fail(t4_ctx *c, int code, const char *fmt, ...);
+#define HIPCHK(ctx, call)                                                                   \
+  do {                                                                                      \
+    hipError_t e_ = (call);                                                                 \
+    if (e_ != hipSuccess) return fail((ctx), T4_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+  } while (0)
+
+// ---- owners of device memory, pinned memory, streams and events ---------------------------------------------------
+// Every handle keeps its GPU resources in these: move-only, freed by the destructor, null after a failed allocation. Members are
+// destroyed in reverse order of declaration, so a handle declares its streams and events before the buffers they work on.
+// What a kernel reads (T4Wide, T4KmerTable, the views, the blobs) stays plain structs of raw pointers, filled from the owners.
+// Device memory: a call's own (freed on every way out of the scope) or a handle's. hipFree waits for the work that still uses it.
+template <class T> struct DevBuf {
+  T *p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) : p(o.p) { o.p = nullptr; }   // (move only)
+  DevBuf &operator=(DevBuf &&o) { swap(o); return *this; }   // (what was here goes with o)
+  ~DevBuf() { free(); }
+  void swap(DevBuf &o) { std::swap(p, o.p); }
+  void free() { if (p) (void)hipFree(p); p = nullptr; }
+  int alloc(t4_ctx *c, size_t count) {   // frees first: a growth that fails leaves nothing behind
+    free();
+    HIPCHK(c, hipMalloc(&p, sizeof(T) * (count ? count : 1)));
+    return T4_OK;
+  }
+  // to `want` elements keeping the first `keep` (stream-ordered copy; the old block is freed once the copy is done)
+  int growKeep(t4_ctx *c, int64_t keep, int64_t want);
+  operator T *() const { return p; }
+};
+// Pinned host memory; with hipHostMallocMapped also its address on the device, asked for once, here.
+template <class T> struct PinnedBuf {
+  T *p = nullptr, *dev = nullptr;
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf &&o) : p(o.p), dev(o.dev) { o.p = o.dev = nullptr; }
+  ~PinnedBuf() { free(); }
+  void swap(PinnedBuf &o) { std::swap(p, o.p); std::swap(dev, o.dev); }
+  void free() { if (p) (void)hipHostFree(p); p = dev = nullptr; }
+  int alloc(t4_ctx *c, size_t count, unsigned flags) {
+    free();
+    HIPCHK(c, hipHostMalloc(&p, sizeof(T) * (count ? count : 1), flags));
+    if (flags & hipHostMallocMapped) {
+      const hipError_t e = hipHostGetDevicePointer((void **)&dev, p, 0);
+      if (e != hipSuccess) { free(); return fail(c, T4_ERR_HIP, "hipHostGetDevicePointer: %s", hipGetErrorString(e)); }
+    }
+    return T4_OK;
+  }
+  operator T *() const { return p; }
+};
+// One stream / one event: made by create() (where the code makes them lazily, that is a no-op from the second time on).
+struct Stream {
+  hipStream_t s = 0;
+  Stream() = default;
+  Stream(const Stream &) = delete;
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  hipError_t create() { return s ? hipSuccess : hipStreamCreate(&s); }
+  operator hipStream_t() const { return s; }
+};
+struct Event {
+  hipEvent_t e = 0;
+  Event() = default;
+  Event(const Event &) = delete;
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  hipError_t create() { return e ? hipSuccess : hipEventCreate(&e); }
+  operator hipEvent_t() const { return e; }
+};
+// The device pools of the wide query (t4_wide.h) with their elements per read slot / per partition: what ensureWide allocates,
+// what wideHalf steps over and what WidePools frees.
+template <class F> void widePoolsPerRead(T4Wide &w, F f) {
+  f(w.seed, T4_WIDE_SEEDS); f(w.bounds, T4_WIDE_MAXP + 1); f(w.uniqPref, w.pcap + 1); f(w.sortTmp, 2 * (size_t)w.pcap); f(w.requeue, 1);
+}
+template <class F> void widePoolsPerPart(T4Wide &w, F f) {
+  f(w.pCnt, 1); f(w.pRead, 1); f(w.pKeys, w.pcap); f(w.gSize, w.pcap); f(w.gInfo, w.pcap); f(w.gCount, 4); f(w.gOff, 2);
+  f(w.pRec, (size_t)w.maxOvPart * 10); f(w.pRecCnt, 1); f(w.mKeys, w.maxOvPart); f(w.mOrd, w.maxOvPart);
+}
+// T4Wide (device pointers + capacities; a copy travels in every call's input blob) as the ctx holds it: the owner of its pools.
+struct WidePools : T4Wide {
+  bool init = false;
+  PinnedBuf<T4Grp> grpHost;        // T4Wide::grpPool is its device address
+  PinnedBuf<unsigned> headHost;    // T4Wide::headBits is its device address
+  WidePools() { memset(static_cast<T4Wide *>(this), 0, sizeof(T4Wide)); }
+  WidePools(const WidePools &) = delete;
+  ~WidePools() {
+    auto drop = [](auto *&p, size_t) { if (p) (void)hipFree(p); p = nullptr; };
+    widePoolsPerRead(*this, drop); widePoolsPerPart(*this, drop);
+  }
+  template <class T> static int alloc(t4_ctx *c, T *&p, size_t count) {   // one pool: freed first, null on failure
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    HIPCHK(c, hipMalloc(&p, sizeof(T) * (count ? count : 1)));
+    return T4_OK;
+  }
+};
+
 // A field of one of the call's two blobs: `count` elements of T, declared once in AqInput / AqHeader. The input blob is packed in
 // pinned staging memory and copied to the device by aqPrologueKernel; the header blob is written on the device and copied into
 // pinned host memory by aqEpilogueKernel.
@@ -118,47 +211,47 @@ struct AqCall {
 
 struct t4_ctx {
   int device = 0, cus = 0;
-  hipStream_t stream = 0;
-  hipStream_t stream2 = 0;   // AddRead queries: reads known to need the global-scratch tier run beside the LDS tier
-  hipEvent_t evIn = 0, evG = 0;
-  hipEvent_t ev[4] = {0, 0, 0, 0};
+  // (streams and events first: the buffers below are freed before these are destroyed)
+  Stream stream;
+  Stream stream2;   // AddRead queries: reads known to need the global-scratch tier run beside the LDS tier; made with evIn, evG by the first call that has such reads
+  Event evIn, evG;
+  Event ev[4];
   std::string err;
   t4_stats stats;
   // scratch
   int maxGrid = 0;
-  int *dpRows = nullptr;
-  unsigned char *dpDir = nullptr;
-  unsigned long long *gKeys = nullptr;
-  unsigned *gPairs = nullptr, *gCand = nullptr;
-  int *gOv = nullptr, *gFin = nullptr;
-  unsigned short *gOrd = nullptr;
+  DevBuf<int> dpRows;
+  DevBuf<unsigned char> dpDir;
+  DevBuf<unsigned long long> gKeys;
+  DevBuf<unsigned> gPairs;
+  DevBuf<int> gOv, gFin;
+  DevBuf<unsigned short> gOrd;
   int gGrid = 0;
-  unsigned long long *hitsKeys = nullptr;
+  DevBuf<unsigned long long> hitsKeys;
   int hitsGrid = 0;
   // per-call buffers (grown on demand)
-  int *lists = nullptr, *listCounts = nullptr, *status = nullptr, *counts = nullptr;
+  DevBuf<int> lists, listCounts, status, counts;
   long long listCap = 0;
-  unsigned long long *hitCounter = nullptr;
-  T4OverlapOut *result = nullptr;
+  DevBuf<unsigned long long> hitCounter;
+  DevBuf<T4OverlapOut> result;
   size_t resultCap = 0, resultBytes = 0;
   // lean path of t4_add_query (small batches, one launch, one round trip)
   int aqCap = 0, aqWpk = 0, aqWnm = 0, aqMax = 0;
-  unsigned char *aqIn = nullptr, *aqOut = nullptr;      // device blobs
-  unsigned char *aqInHost = nullptr, *aqOutHost = nullptr;   // pinned staging, mapped: aqPrologueKernel reads the one, aqEpilogueKernel writes the other
-  unsigned char *aqInHostDev = nullptr, *aqOutHostDev = nullptr;   // their device addresses
-  unsigned *aqFlagHost = nullptr, *aqFlagDev = nullptr;   // pinned word the epilogue of a call leaves the call's sequence number in: what the host waits for
-  unsigned *aqDoneCtr = nullptr;   // device: blocks of a running epilogue that have written their share
+  DevBuf<unsigned char> aqIn, aqOut;      // device blobs
+  PinnedBuf<unsigned char> aqInHost, aqOutHost;   // pinned staging, mapped: aqPrologueKernel reads the one, aqEpilogueKernel writes the other
+  PinnedBuf<unsigned> aqFlag;   // pinned word the epilogue of a call leaves the call's sequence number in: what the host waits for
+  DevBuf<unsigned> aqDoneCtr;   // device: blocks of a running epilogue that have written their share
   unsigned aqSeq = 0;
   size_t aqInBytes = 0, aqOutBytes = 0;
-  unsigned char *aqPool = nullptr, *aqPoolDev = nullptr;   // result records of t4_add_query*: pinned host memory the kernels write
+  PinnedBuf<unsigned char> aqPool;   // result records of t4_add_query*: pinned host memory the kernels write
   int aqPoolCap = 0;
-  unsigned char *candPool = nullptr; T4Cand *candPoolDev = nullptr;   // candidate store of t4_add_query_pool_begin2 (pinned host memory the kernels write)
+  PinnedBuf<unsigned char> candPool;   // candidate store of t4_add_query_pool_begin2 (pinned host memory the kernels write)
   int candCap = 0, candGrows = 0;
   int64_t candRecords = 0;
-  T4OverlapOut *aqRecDev = nullptr;   // device copy of the overlap records + the read of each, for the extension launch
-  int *aqRecRead = nullptr;
+  DevBuf<T4OverlapOut> aqRecDev;   // device copy of the overlap records + the read of each, for the extension launch
+  DevBuf<int> aqRecRead;
   int aqRecCap = 0;
-  int *aqExtAux = nullptr;   // T4CandArgs::extAux of the calls t4_assign_wide makes: one word per record of the result pool
+  DevBuf<int> aqExtAux;   // T4CandArgs::extAux of the calls t4_assign_wide makes: one word per record of the result pool
   int aqExtAuxCap = 0;
   int64_t assignWide[2] = {0, 0};   // last t4_assign_wide call: reads answered by the single-workgroup tiers, reads answered by the wide route
   int64_t aqCalls = 0, aqReads = 0, aqGlobalLaunches = 0, aqGlobalReads = 0, aqRecords = 0;
@@ -186,10 +279,7 @@ struct t4_ctx {
     }
   } aqEnv;
   // the wide query (t4_wide.h): pools of the deferred reads of one call, grown on demand
-  T4Wide wide;               // device pointers + capacities (a copy travels in every call's input blob)
-  bool wideInit = false;
-  unsigned char *grpPoolHost = nullptr;   // pinned; T4Wide::grpPool is its device address
-  unsigned *headBitsHost = nullptr;       // pinned; T4Wide::headBits is its device address
+  WidePools wide;            // device pointers + capacities (a copy travels in every call's input blob)
   std::vector<int32_t> armWords;          // t4_add_query_arm_long_lists: T4CandArgs::rorArm of the next call with restricted re-queries (2 per read)
   std::vector<uint32_t> armHead;          // ... and the head bitmaps its second words point into
   int64_t wideReads = 0, wideParts = 0, wideRetries = 0, wideGroups = 0;
@@ -201,9 +291,9 @@ struct t4_ctx {
   double aqKernelMs = 0;    // HIP-event time of the query kernels of all AddRead query calls (per call: first launch .. last kernel)
   int64_t aqHits = 0;       // _hit records their seed stages emitted (H of SURVEY 8d)
 };
-template <class T> T *AqField<T>::stage(const t4_ctx *c) const { return (T *)(c->aqInHost + off); }
-template <class T> T *AqField<T>::dev(const t4_ctx *c) const { return (T *)((header ? c->aqOut : c->aqIn) + off); }
-template <class T> const T *AqField<T>::host(const t4_ctx *c) const { return (const T *)(c->aqOutHost + off); }
+template <class T> T *AqField<T>::stage(const t4_ctx *c) const { return (T *)(c->aqInHost.p + off); }
+template <class T> T *AqField<T>::dev(const t4_ctx *c) const { return (T *)((header ? c->aqOut.p : c->aqIn.p) + off); }
+template <class T> const T *AqField<T>::host(const t4_ctx *c) const { return (const T *)(c->aqOutHost.p + off); }
 
 struct t4_index {
   t4_ctx *ctx;
@@ -215,21 +305,22 @@ struct t4_index {
   std::unordered_map<std::string, int> dedup;
   bool committed = false;
   // device image
-  uint2 *dTable = nullptr;
-  T4HashEnt *dHtab = nullptr;
-  int2 *dPost = nullptr;
-  T4SeqInfo *dSeqs = nullptr;
-  char *dCons = nullptr;
-  T4PW *dPw = nullptr;
+  Event stEvent;   // (first: destroyed after the buffers)
+  DevBuf<uint2> dTable;
+  DevBuf<T4HashEnt> dHtab;
+  DevBuf<int2> dPost;
+  DevBuf<T4SeqInfo> dSeqs;
+  DevBuf<char> dCons;
+  DevBuf<T4PW> dPw;
   T4IndexView view;
   // live set (t4_index_apply_delta): capacities of the four arrays, staging of one delta
   bool live = false;
-  T4HashEntC *dCtab = nullptr;
+  DevBuf<T4HashEntC> dCtab;
   int64_t capTable = 0, capPost = 0, capBase = 0;
   int capSeq = 0, liveNseq = 0;
-  unsigned char *stHost = nullptr, *stDev = nullptr, *stHostDev = nullptr;   // (stHostDev: the pinned staging buffer as the device addresses it)
+  PinnedBuf<unsigned char> stHost;   // (mapped: a small delta is read by the kernel straight out of it)
+  DevBuf<unsigned char> stDev;
   size_t stCap = 0;
-  hipEvent_t stEvent = 0;
   bool stPending = false;
   uint64_t stEpoch = 0;      // the ctx's syncEpoch when the staging buffer was last handed to a copy
 };
@@ -238,14 +329,12 @@ struct t4_batch {
   t4_ctx *ctx;
   long long n = 0;
   int wpk = 0, wnm = 0, maxLen = 0;
-  unsigned *dPk = nullptr, *dNm = nullptr;
-  int *dLen = nullptr, *dBarcode = nullptr;
+  DevBuf<unsigned> dPk, dNm;
+  DevBuf<int> dLen, dBarcode;
   T4BatchView view;
 };
 
-namespace {
-
-int fail(t4_ctx *c, int code, const char *fmt, ...) {
+static int fail(t4_ctx *c, int code, const char *fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -254,27 +343,16 @@ int fail(t4_ctx *c, int code, const char *fmt, ...) {
   if (c) c->err = buf;
   return code;
 }
-
-#define HIPCHK(ctx, call)                                                                   \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess) return fail((ctx), T4_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-  } while (0)
-
-template <class T> int devAlloc(t4_ctx *c, T **p, size_t count) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  HIPCHK(c, hipMalloc(p, sizeof(T) * (count ? count : 1)));
+template <class T> int DevBuf<T>::growKeep(t4_ctx *c, int64_t keep, int64_t want) {
+  DevBuf<T> grown;
+  HIPCHK(c, hipMalloc(&grown.p, sizeof(T) * (size_t)(want > 0 ? want : 1)));
+  if (p && keep > 0) HIPCHK(c, hipMemcpyAsync(grown.p, p, sizeof(T) * (size_t)keep, hipMemcpyDeviceToDevice, c->stream));
+  if (p) HIPCHK(c, hipStreamSynchronize(c->stream));
+  swap(grown);   // (the old block goes with `grown`)
   return T4_OK;
 }
-// Device memory of one call: freed on every way out of the scope (hipFree waits for the work that still uses it).
-template <class T> struct DevBuf {
-  T *p = nullptr;
-  DevBuf() = default;
-  DevBuf(DevBuf &&o) : p(o.p) { o.p = nullptr; }   // (move only)
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(t4_ctx *c, size_t count) { return devAlloc(c, &p, count); }
-  operator T *() const { return p; }
-};
+namespace {
+
 // A launch whose arguments are turned into the kernel's parameter types first (a DevBuf into its pointer: the buffer itself is not copied).
 template <class T> struct AsIs { typedef T type; };
 template <class... P> void launch(void (*kernel)(P...), int grid, int block, hipStream_t stream, typename AsIs<P>::type... args) {
@@ -302,10 +380,10 @@ inline int nucNum(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 
 // gap-DP scratch for `threads` resident threads (fallback path of bands wider than a wavefront)
 int ensureScratch(t4_ctx *c, int threads) {
   if (threads <= c->maxGrid) return T4_OK;
-  c->maxGrid = 0;   // devAlloc frees first: a growth that fails leaves no capacity behind, and the next call starts over
+  c->maxGrid = 0;   // alloc frees first: a growth that fails leaves no capacity behind, and the next call starts over
   int r;
-  if ((r = devAlloc(c, &c->dpRows, (size_t)(threads / 64 + 1) * 6 * T4_ROWW * 64))) return r;
-  if ((r = devAlloc(c, &c->dpDir, (size_t)threads * T4_DIR_BYTES))) return r;
+  if ((r = c->dpRows.alloc(c, (size_t)(threads / 64 + 1) * 6 * T4_ROWW * 64))) return r;
+  if ((r = c->dpDir.alloc(c, (size_t)threads * T4_DIR_BYTES))) return r;
   c->maxGrid = threads;
   return T4_OK;
 }
@@ -314,11 +392,11 @@ int ensureGlobalTier(t4_ctx *c, int grid) {
   { int g = c->gGrid > 0 ? c->gGrid : 32; while (g < grid) g *= 2; grid = g; }   // 5.4 MB per block: grow rarely
   c->gGrid = 0;
   int r;
-  if ((r = devAlloc(c, &c->gKeys, (size_t)grid * G_CAP))) return r;
-  if ((r = devAlloc(c, &c->gPairs, (size_t)grid * G_CAP * 2))) return r;   // pairs + cand, contiguous per block
-  if ((r = devAlloc(c, &c->gOv, (size_t)grid * G_MAXOV * 10))) return r;
-  if ((r = devAlloc(c, &c->gFin, (size_t)grid * G_MAXOV * 10))) return r;
-  if ((r = devAlloc(c, &c->gOrd, (size_t)grid * G_MAXOV))) return r;
+  if ((r = c->gKeys.alloc(c, (size_t)grid * G_CAP))) return r;
+  if ((r = c->gPairs.alloc(c, (size_t)grid * G_CAP * 2))) return r;   // pairs + cand, contiguous per block
+  if ((r = c->gOv.alloc(c, (size_t)grid * G_MAXOV * 10))) return r;
+  if ((r = c->gFin.alloc(c, (size_t)grid * G_MAXOV * 10))) return r;
+  if ((r = c->gOrd.alloc(c, (size_t)grid * G_MAXOV))) return r;
   c->gGrid = grid;
   return T4_OK;
 }
@@ -326,9 +404,9 @@ int ensurePerCall(t4_ctx *c, long long n) {
   if (n <= c->listCap) return T4_OK;
   c->listCap = 0;
   int r;
-  if ((r = devAlloc(c, &c->lists, (size_t)n * T4_NTIER))) return r;
-  if ((r = devAlloc(c, &c->status, (size_t)n))) return r;
-  if ((r = devAlloc(c, &c->counts, (size_t)n))) return r;
+  if ((r = c->lists.alloc(c, (size_t)n * T4_NTIER))) return r;
+  if ((r = c->status.alloc(c, (size_t)n))) return r;
+  if ((r = c->counts.alloc(c, (size_t)n))) return r;
   c->listCap = n;
   return T4_OK;
 }
@@ -337,25 +415,16 @@ int ensurePerCall(t4_ctx *c, long long n) {
 // pools of the wide query (t4_wide.h): room for `reads` deferred reads, `parts` partitions of `pcap` keys and `groups` dependency
 // records per call; existing contents are never needed across calls, so growing reallocates
 int wideEnv(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
-// The device pools with their elements per read slot / per partition: what ensureWide allocates and what wideHalf steps over.
-template <class F> void widePoolsPerRead(T4Wide &w, F f) {
-  f(w.seed, T4_WIDE_SEEDS); f(w.bounds, T4_WIDE_MAXP + 1); f(w.uniqPref, w.pcap + 1); f(w.sortTmp, 2 * (size_t)w.pcap); f(w.requeue, 1);
-}
-template <class F> void widePoolsPerPart(T4Wide &w, F f) {
-  f(w.pCnt, 1); f(w.pRead, 1); f(w.pKeys, w.pcap); f(w.gSize, w.pcap); f(w.gInfo, w.pcap); f(w.gCount, 4); f(w.gOff, 2);
-  f(w.pRec, (size_t)w.maxOvPart * 10); f(w.pRecCnt, 1); f(w.mKeys, w.maxOvPart); f(w.mOrd, w.maxOvPart);
-}
 size_t wideHeadWords(const T4Wide &w) { return (size_t)(w.pcap + 31) / 32; }   // of T4Wide::headBits (pinned), per read slot
 int ensureWide(t4_ctx *c, int reads, int parts, int groups) {
-  T4Wide &w = c->wide;
-  if (!c->wideInit) {
-    memset(&w, 0, sizeof w);
+  WidePools &w = c->wide;
+  if (!w.init) {
     w.pcap = wideEnv("T4_WIDE_PCAP", 8192);   // testing aid: small partitions, so that small inputs spread over several
     if (w.pcap < 64) w.pcap = 64;
     if (w.pcap > 8192) w.pcap = 8192;
     w.maxOvPart = 1 << T4_WIDE_OVBITS;
     w.maxPartPerRead = T4_WIDE_MAXP;
-    c->wideInit = true;
+    w.init = true;
   }
   int r;
   if (reads > w.maxReads) {
@@ -363,12 +432,11 @@ int ensureWide(t4_ctx *c, int reads, int parts, int groups) {
     while (n < reads) n *= 2;
     w.maxReads = 0;
     r = T4_OK;
-    widePoolsPerRead(w, [&](auto *&p, size_t per) { if (!r) r = devAlloc(c, &p, 2 * (size_t)n * per); });   // (two of everything: wideHalf)
+    widePoolsPerRead(w, [&](auto *&p, size_t per) { if (!r) r = WidePools::alloc(c, p, 2 * (size_t)n * per); });   // (two of everything: wideHalf)
     if (r) return r;
-    if (c->headBitsHost) (void)hipHostFree(c->headBitsHost);
-    c->headBitsHost = nullptr; w.headBits = nullptr;
-    HIPCHK(c, hipHostMalloc(&c->headBitsHost, sizeof(unsigned) * 2 * (size_t)n * wideHeadWords(w), hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer((void **)&w.headBits, c->headBitsHost, 0));
+    w.headBits = nullptr;
+    if ((r = w.headHost.alloc(c, 2 * (size_t)n * wideHeadWords(w), hipHostMallocMapped))) return r;
+    w.headBits = w.headHost.dev;
     w.maxReads = n;
   }
   if (parts > w.maxPart) {
@@ -376,17 +444,16 @@ int ensureWide(t4_ctx *c, int reads, int parts, int groups) {
     while (n < parts) n *= 2;
     w.maxPart = 0;
     r = T4_OK;
-    widePoolsPerPart(w, [&](auto *&p, size_t per) { if (!r) r = devAlloc(c, &p, 2 * (size_t)n * per); });
+    widePoolsPerPart(w, [&](auto *&p, size_t per) { if (!r) r = WidePools::alloc(c, p, 2 * (size_t)n * per); });
     if (r) return r;
     w.maxPart = n;
   }
   if (groups > w.grpCap) {
     int n = w.grpCap > 0 ? w.grpCap : wideEnv("T4_WIDE_GROUPS", 1 << 20);
     while (n < groups) n *= 2;
-    if (c->grpPoolHost) (void)hipHostFree(c->grpPoolHost);
-    c->grpPoolHost = nullptr; w.grpPool = nullptr; w.grpCap = 0;
-    HIPCHK(c, hipHostMalloc(&c->grpPoolHost, sizeof(T4Grp) * 2 * (size_t)n, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer((void **)&w.grpPool, c->grpPoolHost, 0));
+    w.grpPool = nullptr; w.grpCap = 0;
+    if ((r = w.grpHost.alloc(c, 2 * (size_t)n, hipHostMallocMapped))) return r;
+    w.grpPool = w.grpHost.dev;
     w.grpCap = n;
   }
   return T4_OK;
@@ -414,19 +481,18 @@ int t4_init(int device_ordinal, t4_ctx **out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_ordinal < 0 || device_ordinal >= ndev) return T4_ERR_HIP;
   if (hipSetDevice(device_ordinal) != hipSuccess) return T4_ERR_HIP;
-  t4_ctx *c = new t4_ctx();
+  std::unique_ptr<t4_ctx> c(new t4_ctx());   // (every failure below frees what was made so far: the ctx's members own it)
   c->device = device_ordinal;
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device_ordinal) != hipSuccess) { delete c; return T4_ERR_HIP; }
+  if (hipGetDeviceProperties(&prop, device_ordinal) != hipSuccess) return T4_ERR_HIP;
   c->cus = prop.multiProcessorCount;
-  if (hipStreamCreate(&c->stream) != hipSuccess) { delete c; return T4_ERR_HIP; }
-  for (int i = 0; i < 4; ++i) if (hipEventCreate(&c->ev[i]) != hipSuccess) { delete c; return T4_ERR_HIP; }
+  if (c->stream.create() != hipSuccess) return T4_ERR_HIP;
+  for (Event &e : c->ev) if (e.create() != hipSuccess) return T4_ERR_HIP;
   memset(&c->stats, 0, sizeof c->stats);
-  if (hipMalloc(&c->listCounts, sizeof(int) * 16) != hipSuccess || hipMalloc(&c->hitCounter, sizeof(unsigned long long)) != hipSuccess) { delete c; return T4_ERR_HIP; }
-  if (hipHostMalloc(&c->aqFlagHost, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&c->aqFlagDev, c->aqFlagHost, 0) != hipSuccess ||
-      hipMalloc(&c->aqDoneCtr, sizeof(unsigned)) != hipSuccess || hipMemset(c->aqDoneCtr, 0, sizeof(unsigned)) != hipSuccess) { delete c; return T4_ERR_HIP; }
-  *c->aqFlagHost = 0;
-  *out = c;
+  if (c->listCounts.alloc(c.get(), 16) || c->hitCounter.alloc(c.get(), 1)) return T4_ERR_HIP;
+  if (c->aqFlag.alloc(c.get(), 16, hipHostMallocMapped) || c->aqDoneCtr.alloc(c.get(), 1) || hipMemset(c->aqDoneCtr, 0, sizeof(unsigned)) != hipSuccess) return T4_ERR_HIP;
+  *c->aqFlag.p = 0;
+  *out = c.release();
   return T4_OK;
 }
 
@@ -459,30 +525,6 @@ void t4_destroy(t4_ctx *c) {
       fprintf(stderr, "debug counters: gap jobs %llu, banded %llu, wave-DP steps %llu, scratch fallbacks %llu; overhang DPs %llu, of which %llu leave the diagonal\n", dc[0], dc[1], dc[2], dc[3], dc[6], dc[7]);
   }
 #endif
-  void *ptrs[] = {c->dpRows, c->dpDir, c->gKeys, c->gPairs, c->gCand, c->gOv, c->gFin, c->gOrd, c->hitsKeys, c->lists,
-                  c->listCounts, c->status, c->counts, c->hitCounter, c->result, c->aqIn, c->aqOut};
-  if (c->aqInHost) (void)hipHostFree(c->aqInHost);
-  if (c->aqOutHost) (void)hipHostFree(c->aqOutHost);
-  if (c->aqFlagHost) (void)hipHostFree(c->aqFlagHost);
-  if (c->aqDoneCtr) (void)hipFree(c->aqDoneCtr);
-  if (c->aqPool) (void)hipHostFree(c->aqPool);
-  if (c->candPool) (void)hipHostFree(c->candPool);
-  if (c->aqRecDev) (void)hipFree(c->aqRecDev);
-  if (c->aqRecRead) (void)hipFree(c->aqRecRead);
-  if (c->aqExtAux) (void)hipFree(c->aqExtAux);
-  if (c->wideInit) {
-    void *wp[] = {c->wide.seed, c->wide.bounds, c->wide.pCnt, c->wide.pRead, c->wide.pKeys, c->wide.gSize, c->wide.gInfo, c->wide.gCount, c->wide.gOff, c->wide.pRec,
-                  c->wide.pRecCnt, c->wide.uniqPref, c->wide.mKeys, c->wide.mOrd, c->wide.sortTmp, c->wide.requeue};
-    for (void *p : wp) if (p) (void)hipFree(p);
-    if (c->grpPoolHost) (void)hipHostFree(c->grpPoolHost);
-    if (c->headBitsHost) (void)hipHostFree(c->headBitsHost);
-  }
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  for (int i = 0; i < 4; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->evIn) (void)hipEventDestroy(c->evIn);
-  if (c->evG) (void)hipEventDestroy(c->evG);
   delete c;
 }
 
@@ -538,10 +580,6 @@ int t4_index_create(t4_ctx *c, int k, int consider_barcode, t4_index **out) {
 void t4_index_destroy(t4_index *ix) {
   if (!ix) return;
   if (ix->live) (void)hipStreamSynchronize(ix->ctx->stream);
-  void *ptrs[] = {ix->dTable, ix->dHtab, ix->dPost, ix->dSeqs, ix->dCons, ix->dPw, ix->dCtab, ix->stDev};
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  if (ix->stHost) (void)hipHostFree(ix->stHost);
-  if (ix->stEvent) (void)hipEventDestroy(ix->stEvent);
   delete ix;
 }
 
@@ -747,15 +785,13 @@ int commitWithPostings(t4_index *ix, std::vector<Rec> &recs) {
     }
   }
   int r;
-  void *old[] = {ix->dTable, ix->dHtab, ix->dPost, ix->dSeqs, ix->dCons, ix->dPw};
-  for (void *p : old) if (p) (void)hipFree(p);
-  ix->dTable = nullptr; ix->dHtab = nullptr; ix->dPost = nullptr; ix->dSeqs = nullptr; ix->dCons = nullptr; ix->dPw = nullptr;
-  if ((r = devAlloc(c, &ix->dPost, post.size()))) return r;
-  if ((r = devAlloc(c, &ix->dSeqs, infos.size()))) return r;
-  if ((r = devAlloc(c, &ix->dCons, cons.size() + 16))) return r;
-  if ((r = devAlloc(c, &ix->dPw, pw.size()))) return r;
-  if (direct) { if ((r = devAlloc(c, &ix->dTable, table.size()))) return r; }
-  else { if ((r = devAlloc(c, &ix->dHtab, htab.size()))) return r; }
+  ix->dTable.free(); ix->dHtab.free(); ix->dPost.free(); ix->dSeqs.free(); ix->dCons.free(); ix->dPw.free();   // (an image of the other table form leaves none of its arrays)
+  if ((r = ix->dPost.alloc(c, post.size()))) return r;
+  if ((r = ix->dSeqs.alloc(c, infos.size()))) return r;
+  if ((r = ix->dCons.alloc(c, cons.size() + 16))) return r;
+  if ((r = ix->dPw.alloc(c, pw.size()))) return r;
+  if (direct) { if ((r = ix->dTable.alloc(c, table.size()))) return r; }
+  else { if ((r = ix->dHtab.alloc(c, htab.size()))) return r; }
   if (!post.empty()) HIPCHK(c, hipMemcpy(ix->dPost, post.data(), sizeof(int2) * post.size(), hipMemcpyHostToDevice));
   if (!infos.empty()) HIPCHK(c, hipMemcpy(ix->dSeqs, infos.data(), sizeof(T4SeqInfo) * infos.size(), hipMemcpyHostToDevice));
   if (!cons.empty()) HIPCHK(c, hipMemcpy(ix->dCons, cons.data(), cons.size(), hipMemcpyHostToDevice));
@@ -779,19 +815,6 @@ int commitWithPostings(t4_index *ix, std::vector<Rec> &recs) {
 }  // namespace
 
 // ---- live set: patch the device image (see trust4_hip.h) ----------------------------------------------------------
-namespace {
-// grow a device array to `want` elements keeping its first `keep` elements (stream-ordered copy; the old block is freed
-// once the copy is done)
-template <class T> int growKeep(t4_ctx *c, T **p, int64_t keep, int64_t want) {
-  T *np = nullptr;
-  HIPCHK(c, hipMalloc(&np, sizeof(T) * (size_t)(want > 0 ? want : 1)));
-  if (*p && keep > 0) HIPCHK(c, hipMemcpyAsync(np, *p, sizeof(T) * (size_t)keep, hipMemcpyDeviceToDevice, c->stream));
-  if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(*p); }
-  *p = np;
-  return T4_OK;
-}
-}  // namespace
-
 extern "C" {
 
 int t4_index_apply_delta(t4_index *ix, const t4_index_delta *d) {
@@ -805,22 +828,23 @@ int t4_index_apply_delta(t4_index *ix, const t4_index_delta *d) {
   if (d->max_seq_len > T4_MAX_SEQLEN) return fail(c, T4_ERR_UNSUPPORTED, "contig longer than %d", T4_MAX_SEQLEN);
   if (d->post_cap > 0xFFFFFFFFll) return fail(c, T4_ERR_UNSUPPORTED, "more than 2^32 postings");
   int r;
-  if (!ix->stEvent) HIPCHK(c, hipEventCreate(&ix->stEvent));
+  HIPCHK(c, ix->stEvent.create());
   // capacities
   if (d->table_slots != ix->capTable || d->table_rebuilt) {
     if (d->table_slots != ix->capTable) {
-      if (ix->dCtab) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(ix->dCtab); ix->dCtab = nullptr; }
-      HIPCHK(c, hipMalloc(&ix->dCtab, sizeof(T4HashEntC) * (size_t)d->table_slots));
+      if (ix->dCtab) HIPCHK(c, hipStreamSynchronize(c->stream));
+      ix->capTable = 0;
+      if ((r = ix->dCtab.alloc(c, (size_t)d->table_slots))) return r;
       ix->capTable = d->table_slots;
     }
     HIPCHK(c, hipMemsetAsync(ix->dCtab, 0xFF, sizeof(T4HashEntC) * (size_t)ix->capTable, c->stream));   // code ~0 = empty
   }
-  if (d->post_cap > ix->capPost) { int64_t want = d->post_cap + d->post_cap / 2; if ((r = growKeep(c, &ix->dPost, ix->capPost, want))) return r; ix->capPost = want; }
-  if (d->seq_cap > ix->capSeq) { int want = d->seq_cap + d->seq_cap / 2; if ((r = growKeep(c, &ix->dSeqs, (int64_t)ix->capSeq, (int64_t)want))) return r; ix->capSeq = want; }
+  if (d->post_cap > ix->capPost) { int64_t want = d->post_cap + d->post_cap / 2; if ((r = ix->dPost.growKeep(c, ix->capPost, want))) return r; ix->capPost = want; }
+  if (d->seq_cap > ix->capSeq) { int want = d->seq_cap + d->seq_cap / 2; if ((r = ix->dSeqs.growKeep(c, (int64_t)ix->capSeq, (int64_t)want))) return r; ix->capSeq = want; }
   if (d->base_cap > ix->capBase) {
     int64_t want = d->base_cap + d->base_cap / 2;
-    if ((r = growKeep(c, &ix->dCons, ix->capBase, want))) return r;
-    if ((r = growKeep(c, &ix->dPw, ix->capBase, want))) return r;
+    if ((r = ix->dCons.growKeep(c, ix->capBase, want))) return r;
+    if ((r = ix->dPw.growKeep(c, ix->capBase, want))) return r;
     ix->capBase = want;
   }
   // staging: descriptors, then the payload (8-byte aligned pieces)
@@ -844,15 +868,13 @@ int t4_index_apply_delta(t4_index *ix, const t4_index_delta *d) {
     if (ix->stPending && ix->stEpoch == c->syncEpoch) { HIPCHK(c, hipStreamSynchronize(c->stream)); ++c->syncEpoch; }
     ix->stPending = false;
     if (bytes > ix->stCap) {
-      if (ix->stHost) (void)hipHostFree(ix->stHost);
-      if (ix->stDev) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(ix->stDev); }
-      ix->stHost = nullptr; ix->stDev = nullptr;
-      ix->stCap = bytes * 2 > ((size_t)1 << 20) ? bytes * 2 : ((size_t)1 << 20);
-      HIPCHK(c, hipHostMalloc(&ix->stHost, ix->stCap, hipHostMallocMapped));
-      HIPCHK(c, hipHostGetDevicePointer((void **)&ix->stHostDev, ix->stHost, 0));
-      HIPCHK(c, hipMalloc(&ix->stDev, ix->stCap));
+      const size_t ncap = bytes * 2 > ((size_t)1 << 20) ? bytes * 2 : ((size_t)1 << 20);
+      if (ix->stDev) HIPCHK(c, hipStreamSynchronize(c->stream));
+      ix->stCap = 0;
+      if ((r = ix->stHost.alloc(c, ncap, hipHostMallocMapped)) || (r = ix->stDev.alloc(c, ncap))) return r;
+      ix->stCap = ncap;
     }
-    T4CopyDesc *desc = (T4CopyDesc *)ix->stHost;
+    T4CopyDesc *desc = (T4CopyDesc *)ix->stHost.p;
     size_t at = al8(sizeof(T4CopyDesc) * nDesc), nd = 0;
     for (int64_t i = 0; i < d->n_slots; ++i) {
       if (d->slot[i] < 0 || d->slot[i] >= ix->capTable) return fail(c, T4_ERR_ARG, "table slot %lld outside the table", (long long)d->slot[i]);
@@ -905,7 +927,7 @@ int t4_index_apply_delta(t4_index *ix, const t4_index_delta *d) {
     ix->stPending = true; ix->stEpoch = c->syncEpoch;
     int grid = (int)((nd + 3) / 4);
     if (grid > c->cus * 8) grid = c->cus * 8;
-    const unsigned char *stg = direct ? ix->stHostDev : ix->stDev;
+    const unsigned char *stg = direct ? ix->stHost.dev : ix->stDev.p;
     hipLaunchKernelGGL(t4k::deltaKernel, dim3(grid), dim3(256), 0, c->stream, stg, (const T4CopyDesc *)stg, (int)nd);
     HIPCHK(c, hipGetLastError());
   }
@@ -943,7 +965,7 @@ int t4_reads_upload_flags(t4_ctx *c, const char *bases, const int64_t *offsets, 
     if (l > T4_MAXL) return fail(c, T4_ERR_UNSUPPORTED, "read %lld is %lld bp; this engine takes reads up to %d bp", (long long)i, (long long)l, T4_MAXL);
     if (l > maxLen) maxLen = (int)l;
   }
-  std::unique_ptr<t4_batch, void (*)(t4_batch *)> b(new t4_batch(), t4_batch_destroy);   // (and its device buffers, on every way out but the last)
+  std::unique_ptr<t4_batch> b(new t4_batch());   // (and its device buffers, on every way out but the last)
   b->ctx = c; b->n = n; b->maxLen = maxLen;
   b->wpk = (maxLen + 15) / 16; b->wnm = (maxLen + 31) / 32;
   if (b->wpk == 0) b->wpk = 1;
@@ -990,14 +1012,14 @@ int t4_reads_upload_flags(t4_ctx *c, const char *bases, const int64_t *offsets, 
   }
   int r;
   // + 4 words: the packed k-mer extraction reads one word past a read's row (masked out), also for the last read
-  if ((r = devAlloc(c, &b->dPk, pk.size() + 4)) || (r = devAlloc(c, &b->dNm, nm.size() + 4)) || (r = devAlloc(c, &b->dLen, len.size()))) return r;
+  if ((r = b->dPk.alloc(c, pk.size() + 4)) || (r = b->dNm.alloc(c, nm.size() + 4)) || (r = b->dLen.alloc(c, len.size()))) return r;
   if (n > 0) {
     HIPCHK(c, hipMemcpy(b->dPk, pk.data(), sizeof(unsigned) * pk.size(), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(b->dNm, nm.data(), sizeof(unsigned) * nm.size(), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(b->dLen, len.data(), sizeof(int) * len.size(), hipMemcpyHostToDevice));
   }
   if (barcode) {
-    if ((r = devAlloc(c, &b->dBarcode, (size_t)n))) return r;
+    if ((r = b->dBarcode.alloc(c, (size_t)n))) return r;
     if (n > 0) HIPCHK(c, hipMemcpy(b->dBarcode, barcode, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
   }
   b->view.pk = b->dPk; b->view.nm = b->dNm; b->view.len = b->dLen; b->view.barcode = b->dBarcode;
@@ -1006,12 +1028,7 @@ int t4_reads_upload_flags(t4_ctx *c, const char *bases, const int64_t *offsets, 
   return T4_OK;
 }
 
-void t4_batch_destroy(t4_batch *b) {
-  if (!b) return;
-  void *ptrs[] = {b->dPk, b->dNm, b->dLen, b->dBarcode};
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  delete b;
-}
+void t4_batch_destroy(t4_batch *b) { delete b; }
 int64_t t4_batch_size(const t4_batch *b) { return b ? b->n : 0; }
 
 }  // extern "C"
@@ -1078,7 +1095,7 @@ int runQuery(t4_index *ix, t4_batch *b, T4QueryArgs qa, bool useBarcode, bool no
     int grid = grids[t] < cnt ? grids[t] : cnt;
     if (t == T4_NTIER - 1) {
       if ((r = ensureGlobalTier(c, grids[T4_NTIER - 1]))) return r;
-      wk.gKeys = c->gKeys; wk.gPairs = c->gPairs; wk.gCand = c->gCand; wk.gOv = c->gOv; wk.gFin = c->gFin; wk.gOrd = c->gOrd;
+      wk.gKeys = c->gKeys; wk.gPairs = c->gPairs; wk.gCand = nullptr; wk.gOv = c->gOv; wk.gFin = c->gFin; wk.gOrd = c->gOrd;
       wk.gCap = G_CAP; wk.gMaxOv = G_MAXOV;
       launchTier<0, 0, G_THREADS>(grid, c->stream, ix->view, b->view, wk, qa);
     }
@@ -1112,7 +1129,7 @@ int runQuery(t4_index *ix, t4_batch *b, T4QueryArgs qa, bool useBarcode, bool no
 int ensureResult(t4_ctx *c, size_t records) {
   if (records <= c->resultCap) return T4_OK;
   c->resultCap = 0;
-  int r = devAlloc(c, &c->result, records);
+  int r = c->result.alloc(c, records);
   if (r) return r;
   c->resultCap = records;
   return T4_OK;
@@ -1163,7 +1180,7 @@ int t4_hits(t4_index *ix, t4_batch *b, int strand, int allow_total_skip, int64_t
   int grid = c->cus * 2;
   if ((long long)grid > n) grid = (int)n;
   const int HCAP = 65536;
-  if (grid > c->hitsGrid) { c->hitsGrid = 0; if ((r = devAlloc(c, &c->hitsKeys, (size_t)grid * HCAP))) return r; c->hitsGrid = grid; }
+  if (grid > c->hitsGrid) { c->hitsGrid = 0; if ((r = c->hitsKeys.alloc(c, (size_t)grid * HCAP))) return r; c->hitsGrid = grid; }
   if ((r = ensurePerCall(c, n))) return r;
   DevBuf<long long> dOff;
   DevBuf<T4HitOut> dHits;
@@ -1307,22 +1324,21 @@ int t4_process_pairs(t4_ctx *c, int n, const int64_t *off1, const char *r1, cons
 // ---- KmerCount (KmerCount.hpp) on the device ------------------------------------------------------------------------
 struct t4_kmer_counter {
   t4_ctx *ctx = nullptr;
-  T4KmerTable tb{};
+  T4KmerTable tb{};   // (a kernel argument: plain pointers into the four blocks below)
+  DevBuf<unsigned long long> keys;
+  DevBuf<unsigned> cnt;
+  DevBuf<int> overflow;
+  DevBuf<unsigned long long> used;
   unsigned long long slots = 0, maxSlots = 0;
 };
 
 namespace {
 // a table of `slots` slots (a power of two), zeroed; the counter's small words (overflow flag, used-slot count) stay as they are
-int kmerTableAlloc(t4_ctx *c, unsigned long long slots, T4KmerTable &tb) {
-  tb.keys = nullptr; tb.cnt = nullptr;
-  if (hipMalloc(&tb.keys, sizeof(unsigned long long) * slots) != hipSuccess || hipMalloc(&tb.cnt, sizeof(unsigned) * slots) != hipSuccess) {
-    if (tb.keys) (void)hipFree(tb.keys);
-    tb.keys = nullptr;
-    return fail(c, T4_ERR_HIP, "k-mer count table: no device memory for %llu slots", slots);
-  }
-  HIPCHK(c, hipMemsetAsync(tb.keys, 0, sizeof(unsigned long long) * slots, c->stream));
-  HIPCHK(c, hipMemsetAsync(tb.cnt, 0, sizeof(unsigned) * slots, c->stream));
-  tb.mask = slots - 1;
+int kmerTableAlloc(t4_ctx *c, unsigned long long slots, T4KmerTable &tb, DevBuf<unsigned long long> &keys, DevBuf<unsigned> &cnt) {
+  if (keys.alloc(c, slots) || cnt.alloc(c, slots)) { keys.free(); return fail(c, T4_ERR_HIP, "k-mer count table: no device memory for %llu slots", slots); }
+  HIPCHK(c, hipMemsetAsync(keys, 0, sizeof(unsigned long long) * slots, c->stream));
+  HIPCHK(c, hipMemsetAsync(cnt, 0, sizeof(unsigned) * slots, c->stream));
+  tb.keys = keys; tb.cnt = cnt; tb.mask = slots - 1;
   return T4_OK;
 }
 // Room for `incoming` more k-mers at a load of at most 0.6: the table is rehashed on the device into one four times as large as
@@ -1339,14 +1355,16 @@ int kmerEnsureRoom(t4_kmer_counter *kc, unsigned long long incoming, bool raiseM
     unsigned long long ns = kc->slots * 4ull;
     if (ns > kc->maxSlots) ns = kc->maxSlots;
     T4KmerTable to = kc->tb;
+    DevBuf<unsigned long long> keys;   // (the new pair; after the swap below the old one, which goes with these two)
+    DevBuf<unsigned> cnt;
     int r;
-    if ((r = kmerTableAlloc(c, ns, to))) return r;
+    if ((r = kmerTableAlloc(c, ns, to, keys, cnt))) return r;
     const unsigned long long blocks = (kc->slots + 255ull) / 256ull;
     const int grid = (int)(blocks < (unsigned long long)c->cus * 16ull ? blocks : (unsigned long long)c->cus * 16ull);
     hipLaunchKernelGGL(t4k::kmerRehashKernel, dim3(grid), dim3(256), 0, c->stream, kc->tb, to);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(kc->tb.keys); (void)hipFree(kc->tb.cnt);
+    kc->keys.swap(keys); kc->cnt.swap(cnt);
     kc->tb = to; kc->slots = ns;
   }
   return T4_OK;
@@ -1367,30 +1385,21 @@ int t4_kmer_count_create(t4_ctx *c, int k, int64_t max_kmers, int per_barcode, t
 #ifdef T4_TEST_KNOBS   // (emulator / test builds only)
   if (getenv("T4_KC_SLOTS")) { slots = 1024; const unsigned long long want = strtoull(getenv("T4_KC_SLOTS"), nullptr, 10); while (slots < want && slots < maxSlots) slots <<= 1; }   // testing aid: a small first table (the growth path)
 #endif
-  t4_kmer_counter *kc = new t4_kmer_counter;
+  std::unique_ptr<t4_kmer_counter> kc(new t4_kmer_counter);
   kc->ctx = c; kc->slots = slots; kc->maxSlots = maxSlots;
   kc->tb.k = k; kc->tb.perBarcode = per_barcode ? 1 : 0;
-  kc->tb.overflow = nullptr; kc->tb.used = nullptr;
-  int r = kmerTableAlloc(c, slots, kc->tb);
-  if (r || hipMalloc(&kc->tb.overflow, sizeof(int)) != hipSuccess || hipMalloc(&kc->tb.used, sizeof(unsigned long long)) != hipSuccess) {
-    t4_kmer_count_destroy(kc);
-    return r ? r : fail(c, T4_ERR_HIP, "t4_kmer_count_create: no device memory");
-  }
+  int r = kmerTableAlloc(c, slots, kc->tb, kc->keys, kc->cnt);
+  if (r) return r;
+  if (kc->overflow.alloc(c, 1) || kc->used.alloc(c, 1)) return fail(c, T4_ERR_HIP, "t4_kmer_count_create: no device memory");
+  kc->tb.overflow = kc->overflow; kc->tb.used = kc->used;
   HIPCHK(c, hipMemsetAsync(kc->tb.overflow, 0, sizeof(int), c->stream));
   HIPCHK(c, hipMemsetAsync(kc->tb.used, 0, sizeof(unsigned long long), c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  *out = kc;
+  *out = kc.release();
   return T4_OK;
 }
 
-void t4_kmer_count_destroy(t4_kmer_counter *kc) {
-  if (!kc) return;
-  if (kc->tb.keys) (void)hipFree(kc->tb.keys);
-  if (kc->tb.cnt) (void)hipFree(kc->tb.cnt);
-  if (kc->tb.overflow) (void)hipFree(kc->tb.overflow);
-  if (kc->tb.used) (void)hipFree(kc->tb.used);
-  delete kc;
-}
+void t4_kmer_count_destroy(t4_kmer_counter *kc) { delete kc; }
 
 int t4_kmer_count_add(t4_kmer_counter *kc, t4_batch *b) {
   if (!kc || !b) return T4_ERR_ARG;
@@ -1777,14 +1786,11 @@ double secondsSince(std::chrono::steady_clock::time_point t0) { return std::chro
 // at once, on a second stream beside the LDS tier; on return nonzero for every read the global-scratch tier served.
 int aqLaunch(t4_ctx *c);
 // a blob's device copy and its pinned, mapped twin on the host: room for twice what the call needs when they have to grow
-int growBlob(t4_ctx *c, size_t need, size_t *cap, unsigned char **dev, unsigned char **host, unsigned char **hostDev) {
+int growBlob(t4_ctx *c, size_t need, size_t *cap, DevBuf<unsigned char> &dev, PinnedBuf<unsigned char> &host) {
   if (need <= *cap) return T4_OK;
-  if (*dev) (void)hipFree(*dev);
-  if (*host) (void)hipHostFree(*host);
-  *dev = nullptr; *host = nullptr;
-  HIPCHK(c, hipMalloc(dev, need * 2));
-  HIPCHK(c, hipHostMalloc(host, need * 2, hipHostMallocMapped));
-  HIPCHK(c, hipHostGetDevicePointer((void **)hostDev, *host, 0));
+  *cap = 0;
+  int r;
+  if ((r = dev.alloc(c, need * 2)) || (r = host.alloc(c, need * 2, hipHostMallocMapped))) return r;
   *cap = need * 2;
   return T4_OK;
 }
@@ -1828,7 +1834,7 @@ int aqBegin(t4_ctx *c, const T4IndexView &base, const T4IndexView *views, const 
   for (auto &h : hdr.wide) { hdr.add(h.ctl, T4_WC_WORDS); hdr.add(h.plan, nW); hdr.add(h.stat, T4_WIDE_STAT * nW); }
   q.wideSafety = c->wideSafetyKeep;
   int r;
-  if ((r = growBlob(c, in.bytes, &c->aqInBytes, &c->aqIn, &c->aqInHost, &c->aqInHostDev)) || (r = growBlob(c, hdr.bytes, &c->aqOutBytes, &c->aqOut, &c->aqOutHost, &c->aqOutHostDev))) return r;
+  if ((r = growBlob(c, in.bytes, &c->aqInBytes, c->aqIn, c->aqInHost)) || (r = growBlob(c, hdr.bytes, &c->aqOutBytes, c->aqOut, c->aqOutHost))) return r;
   const auto tp0 = std::chrono::steady_clock::now();
   memset(c->aqInHost, 0, q.in.bytes);
   if (q.hasArm) {   // (consumed: the arming holds for this call alone)
@@ -1915,8 +1921,8 @@ int aqLaunchEpilogue(t4_ctx *c) {   // the header block into pinned host memory,
   const int grid = clampi((int)((outW + 4095) / 4096), 1, 64);
   ++c->aqSeq;
   if (c->aqSeq == 0) c->aqSeq = 1;
-  hipLaunchKernelGGL(t4k::aqEpilogueKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned long long *)c->aqOut, (unsigned long long *)c->aqOutHostDev, outW,
-                     c->aqDoneCtr, c->aqFlagDev, c->aqSeq);
+  hipLaunchKernelGGL(t4k::aqEpilogueKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned long long *)c->aqOut.p, (unsigned long long *)c->aqOutHost.dev, outW,
+                     c->aqDoneCtr.p, c->aqFlag.dev, c->aqSeq);
   HIPCHK(c, hipGetLastError());
   return T4_OK;
 }
@@ -1929,14 +1935,12 @@ int aqLaunch(t4_ctx *c) {
   int r;
   if (!c->aqPool) {
     if (!c->aqPoolCap) c->aqPoolCap = c->aqEnv.poolCap > 0 ? c->aqEnv.poolCap : 1 << 16;   // (testing aid: a small pool forces the grow-and-repeat path)
-    HIPCHK(c, hipHostMalloc(&c->aqPool, (size_t)c->aqPoolCap * (2 * sizeof(t4_overlap) + sizeof(int32_t)), hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer((void **)&c->aqPoolDev, c->aqPool, 0));
+    if ((r = c->aqPool.alloc(c, (size_t)c->aqPoolCap * (2 * sizeof(t4_overlap) + sizeof(int32_t)), hipHostMallocMapped))) return r;
   }
   const size_t rec = (size_t)c->aqPoolCap;
   if (q.wantCands && !c->candPool) {
     if (!c->candCap) c->candCap = c->aqEnv.candCap > 0 ? c->aqEnv.candCap : 1 << 18;   // (testing aid: a small pool forces the grow-and-repeat path)
-    HIPCHK(c, hipHostMalloc(&c->candPool, sizeof(T4Cand) * (size_t)c->candCap, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer((void **)&c->candPoolDev, c->candPool, 0));
+    if ((r = c->candPool.alloc(c, sizeof(T4Cand) * (size_t)c->candCap, hipHostMallocMapped))) return r;
   }
   q.tf0 = std::chrono::steady_clock::now();
   auto tl_ = q.tf0;
@@ -1965,13 +1969,13 @@ int aqLaunch(t4_ctx *c) {
     if (q.keepExtAux) {   // (sized with the pool: a call repeated with a larger pool comes through here again)
       if (c->aqExtAuxCap < c->aqPoolCap) {
         c->aqExtAuxCap = 0;
-        if ((r = devAlloc(c, &c->aqExtAux, (size_t)c->aqPoolCap))) return r;
+        if ((r = c->aqExtAux.alloc(c, (size_t)c->aqPoolCap))) return r;
         c->aqExtAuxCap = c->aqPoolCap;
       }
       cs.extAux = c->aqExtAux;
     }
     if (q.wantCands) {
-      cs.candOut = c->candPoolDev; cs.candCap = c->candCap; cs.candCursor = &tail->candCursor; cs.candOverflow = &tail->candOverflow;
+      cs.candOut = (T4Cand *)c->candPool.dev; cs.candCap = c->candCap; cs.candCursor = &tail->candCursor; cs.candOverflow = &tail->candOverflow;
       cs.candBase = q.hdr.candBase.dev(c); cs.candCnt = q.hdr.candCnt.dev(c);
     }
     *q.in.cs.stage(c) = cs;
@@ -1981,8 +1985,8 @@ int aqLaunch(t4_ctx *c) {
     const unsigned long long inW = q.in.bytes >> 3, outW = q.hdr.bytes >> 3;
     const unsigned long long most = inW > outW ? inW : outW;
     const int grid = clampi((int)((most + 2047) / 2048), 1, c->cus * 4);
-    hipLaunchKernelGGL(t4k::aqPrologueKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned long long *)c->aqInHostDev, (unsigned long long *)c->aqIn, inW,
-                       (unsigned long long *)c->aqOut, outW);
+    hipLaunchKernelGGL(t4k::aqPrologueKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned long long *)c->aqInHost.dev, (unsigned long long *)c->aqIn.p, inW,
+                       (unsigned long long *)c->aqOut.p, outW);
     HIPCHK(c, hipGetLastError());
   }
   lapL(1);
@@ -1993,7 +1997,7 @@ int aqLaunch(t4_ctx *c) {
   memset(&qa, 0, sizeof qa);
   qa.mode = 4; qa.skipRepeats = q.skipRepeats; qa.maxPerRead = 0;
   qa.counts = q.hdr.counts.dev(c);
-  qa.out = (T4OverlapOut *)c->aqPoolDev; qa.outExt = qa.out + rec; qa.ret = (int *)(qa.outExt + rec);
+  qa.out = (T4OverlapOut *)c->aqPool.dev; qa.outExt = qa.out + rec; qa.ret = (int *)(qa.outExt + rec);
   qa.outBase = q.hdr.outBase.dev(c); qa.poolCursor = &tail->poolCursor; qa.poolCap = c->aqPoolCap;
   qa.strandPerRead = q.in.strand.dev(c); qa.factorPerRead = q.in.factor.dev(c);
   qa.readTicks = q.hdr.ticks.dev(c); qa.statsStable = q.hdr.stable.dev(c); qa.aux = q.hdr.aux.dev(c); qa.n4 = q.hdr.n4.dev(c);
@@ -2009,7 +2013,7 @@ int aqLaunch(t4_ctx *c) {
   if (extendLater) {
     if (c->aqRecCap < c->aqPoolCap) {
       c->aqRecCap = 0;
-      if ((r = devAlloc(c, &c->aqRecDev, (size_t)c->aqPoolCap)) || (r = devAlloc(c, &c->aqRecRead, (size_t)c->aqPoolCap))) return r;
+      if ((r = c->aqRecDev.alloc(c, (size_t)c->aqPoolCap)) || (r = c->aqRecRead.alloc(c, (size_t)c->aqPoolCap))) return r;
       c->aqRecCap = c->aqPoolCap;
     }
     qa.extendLater = deferMin; qa.outDev = c->aqRecDev; qa.recRead = c->aqRecRead;
@@ -2033,7 +2037,7 @@ int aqLaunch(t4_ctx *c) {
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
   lapL(5);
   if (nDirect > 0) {   // beside the LDS tier, on the second stream (its own blocks of the DP scratch)
-    if (!c->stream2) { HIPCHK(c, hipStreamCreate(&c->stream2)); HIPCHK(c, hipEventCreate(&c->evIn)); HIPCHK(c, hipEventCreate(&c->evG)); }
+    if (!c->stream2) { HIPCHK(c, c->stream2.create()); HIPCHK(c, c->evIn.create()); HIPCHK(c, c->evG.create()); }
     HIPCHK(c, hipEventRecord(c->evIn, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evIn, 0));
     T4Work wd = wk;
@@ -2047,7 +2051,7 @@ int aqLaunch(t4_ctx *c) {
       launchWideSeed(c, c->stream2, wa, wd, wd.list, nDirect, q.skipRepeats ? 1 : 0);
       launchWide(c, c->stream2, wa, wd, wideGridParts(c, 2 * c->wideRecentParts + 4 * nDirect + 4), wideGridReads(c, nDirect));
     } else {
-      wd.gKeys = c->gKeys; wd.gPairs = c->gPairs; wd.gCand = c->gCand; wd.gOv = c->gOv; wd.gFin = c->gFin; wd.gOrd = c->gOrd;
+      wd.gKeys = c->gKeys; wd.gPairs = c->gPairs; wd.gCand = nullptr; wd.gOv = c->gOv; wd.gFin = c->gFin; wd.gOrd = c->gOrd;
       wd.gCap = G_CAP; wd.gMaxOv = G_MAXOV;
       launchTier<0, 0, G_THREADS>(nDirect, c->stream2, q.base, bv, wd, qa);
       ++c->aqGlobalLaunches; c->aqGlobalReads += nDirect;
@@ -2061,7 +2065,7 @@ int aqLaunch(t4_ctx *c) {
     else {   // a read that outgrows the LDS arrays goes on in global scratch inside the same launch
       T4Work wf = wk;
       const size_t skip = q.wide ? 0 : (size_t)nDirect;   // the blocks of a concurrent global-tier launch own the first slices
-      wf.gKeys = c->gKeys + skip * G_CAP; wf.gPairs = c->gPairs + skip * G_CAP * 2; wf.gCand = c->gCand;
+      wf.gKeys = c->gKeys + skip * G_CAP; wf.gPairs = c->gPairs + skip * G_CAP * 2; wf.gCand = nullptr;
       wf.gOv = c->gOv + skip * G_MAXOV * 10; wf.gFin = c->gFin + skip * G_MAXOV * 10; wf.gOrd = c->gOrd + skip * G_MAXOV;
       wf.gCap = G_CAP; wf.gMaxOv = G_MAXOV;
       launchTier<8192, 512, 512>(grid0, c->stream, q.base, bv, wf, qa);
@@ -2089,12 +2093,12 @@ int aqLaunch(t4_ctx *c) {
 int aqWait(t4_ctx *c) {
   const unsigned want = c->aqSeq;
   for (unsigned long long spin = 1;; ++spin) {
-    if (__atomic_load_n(c->aqFlagHost, __ATOMIC_ACQUIRE) == want) return T4_OK;
+    if (__atomic_load_n(c->aqFlag.p, __ATOMIC_ACQUIRE) == want) return T4_OK;
     if ((spin & 0xFFFFull) == 0) {
       const hipError_t e = hipStreamQuery(c->stream);
       if (e == hipSuccess) {
-        if (__atomic_load_n(c->aqFlagHost, __ATOMIC_ACQUIRE) == want) return T4_OK;
-        return fail(c, T4_ERR_HIP, "the stream of an AddRead query call is idle but its epilogue never reported (word %u, expected %u)", *c->aqFlagHost, want);
+        if (__atomic_load_n(c->aqFlag.p, __ATOMIC_ACQUIRE) == want) return T4_OK;
+        return fail(c, T4_ERR_HIP, "the stream of an AddRead query call is idle but its epilogue never reported (word %u, expected %u)", *c->aqFlag.p, want);
       }
       if (e != hipErrorNotReady) return fail(c, T4_ERR_HIP, "AddRead query call: %s", hipGetErrorString(e));
     }
@@ -2104,7 +2108,7 @@ int aqWait(t4_ctx *c) {
 // has the call in flight finished on the device? (1 yes or nothing in flight, 0 not yet)
 int aqDone(t4_ctx *c) {
   if (!c->aq.active) return 1;
-  return __atomic_load_n(c->aqFlagHost, __ATOMIC_ACQUIRE) == c->aqSeq ? 1 : 0;
+  return __atomic_load_n(c->aqFlag.p, __ATOMIC_ACQUIRE) == c->aqSeq ? 1 : 0;
 }
 
 // A launch that aqEnd adds to the call once its header is on the host: between the ctx's two events, with the extensions of the
@@ -2136,8 +2140,8 @@ template <class Launch> int aqRerun(t4_ctx *c, Launch launchIt) {
 }
 // The whole call again, after the caller made room for what overflowed. `pool`: a pinned pool to drop (aqLaunch allocates it anew at
 // the capacity the caller has set).
-int aqRepeat(t4_ctx *c, unsigned char **pool = nullptr) {
-  if (pool) { (void)hipHostFree(*pool); *pool = nullptr; }
+int aqRepeat(t4_ctx *c, PinnedBuf<unsigned char> *pool = nullptr) {
+  if (pool) pool->free();
   ++c->aq.attempt;
   return aqLaunch(c);
 }
@@ -2283,7 +2287,7 @@ int aqEnd(t4_ctx *c, AqResult *res) {
       if ((r = ensureScratch(c, (overflow > c->cus * 2 ? overflow : c->cus * 2) * G_THREADS))) return r;
       T4Work w2 = wk;
       w2.list = overflowList->dev(c); w2.nList = overflow; w2.nextList = nullptr; w2.nextCount = nullptr;
-      w2.gKeys = c->gKeys; w2.gPairs = c->gPairs; w2.gCand = c->gCand; w2.gOv = c->gOv; w2.gFin = c->gFin; w2.gOrd = c->gOrd;
+      w2.gKeys = c->gKeys; w2.gPairs = c->gPairs; w2.gCand = nullptr; w2.gOv = c->gOv; w2.gFin = c->gFin; w2.gOrd = c->gOrd;
       w2.gCap = G_CAP; w2.gMaxOv = G_MAXOV;
       w2.dpRows = c->dpRows; w2.dpDir = c->dpDir;
       if ((r = aqRerun(c, [&] { launchTier<0, 0, G_THREADS>(overflow, c->stream, q.base, q.bv, w2, q.qa); }))) return r;
@@ -2309,13 +2313,13 @@ int aqEnd(t4_ctx *c, AqResult *res) {
       if (q.attempt >= 12) return fail(c, T4_ERR_UNSUPPORTED, "candidate pool of %d records overflows", c->candCap);
       while ((unsigned)c->candCap < tail->candCursor && c->candCap < (1 << 29)) c->candCap *= 2;
       c->candCap *= 2;
-      c->candPoolDev = nullptr; ++c->candGrows;
+      ++c->candGrows;
       if ((r = aqRepeat(c, &c->candPool))) return r;
       continue;
     }
     if (poolFull) {   // more result records than the pool holds: a larger pool, and the whole call again
       if (q.attempt >= 8) return fail(c, T4_ERR_UNSUPPORTED, "result pool of %d records overflows", c->aqPoolCap);
-      c->aqPoolDev = nullptr; c->aqPoolCap *= 4; ++c->aqPoolGrows;
+      c->aqPoolCap *= 4; ++c->aqPoolGrows;
       if ((r = aqRepeat(c, &c->aqPool))) return r;
       continue;
     }
@@ -2327,7 +2331,7 @@ int aqEnd(t4_ctx *c, AqResult *res) {
     c->aqLastTicks = hdr.ticks.host(c); c->aqLastN = n;
     c->aqLastStable = hdr.stable.host(c);
     res->counts = hdr.counts.host(c); res->base = hdr.outBase.host(c);
-    res->ov = (const t4_overlap *)c->aqPool; res->ext = res->ov + rec; res->ret = (const int32_t *)(res->ext + rec);
+    res->ov = (const t4_overlap *)c->aqPool.p; res->ext = res->ov + rec; res->ret = (const int32_t *)(res->ext + rec);
     return T4_OK;
   }
 }
@@ -2399,7 +2403,7 @@ int assignWidePass2(t4_index *ix, t4_batch *b, const std::vector<int64_t> &todo,
     if ((r = aqEnd(c, &res))) return r;
     const AqCall &q = c->aq;
     const size_t rec = (size_t)c->aqPoolCap;
-    const T4OverlapOut *ov = (const T4OverlapOut *)c->aqPoolDev;
+    const T4OverlapOut *ov = (const T4OverlapOut *)c->aqPool.dev;
     launch(t4k::assignPickKernel, m, T4_PICK_THREADS, c->stream, m, q.hdr.counts.dev(c), q.hdr.outBase.dev(c), q.in.len.dev(c), ov,
            ov + rec, (const int *)(ov + 2 * rec), c->aqExtAux, c->aqPoolCap, dRet, dOut);
     HIPCHK(c, hipGetLastError());
@@ -2453,7 +2457,7 @@ int t4_add_query_groups(t4_ctx *c, int i, const t4_grp **groups, int *n, int *hu
   if (at.half < 0) return 0;
   const T4WidePlan &plan = q.hdr.wide[at.half].plan.host(c)[at.slot];
   const int *st = q.hdr.wide[at.half].stat.host(c) + (size_t)at.slot * T4_WIDE_STAT;
-  *groups = (const t4_grp *)c->grpPoolHost + (at.half ? (size_t)c->wide.grpCap : 0) + plan.grpBase;
+  *groups = (const t4_grp *)c->wide.grpHost.p + (at.half ? (size_t)c->wide.grpCap : 0) + plan.grpBase;
   *n = st[WS_GROUPS];
   if (huge) *huge = plan.huge;
   if (n4) *n4 = st[WS_N4];
@@ -2468,13 +2472,13 @@ int t4_add_query_groups(t4_ctx *c, int i, const t4_grp **groups, int *n, int *hu
 int t4_add_query_head(t4_ctx *c, int i, int *m, const uint32_t **bits, int *ror) {
   if (!c || !m || !bits || !ror) return T4_ERR_ARG;
   const AqCall &q = c->aq;
-  if (!q.wide || !c->aqOutHost || !c->headBitsHost) return 0;
+  if (!q.wide || !c->aqOutHost || !c->wide.headHost) return 0;
   const WideSlot at = findWideSlot(c, i);
   if (at.half < 0 || !q.hdr.wide[at.half].plan.host(c)[at.slot].huge) return 0;
   const int *st = q.hdr.wide[at.half].stat.host(c) + (size_t)at.slot * T4_WIDE_STAT;
   *m = st[WS_M];
   *ror = (st[WS_ROR] ? 1 : 0) | (st[WS_ROR + 1] ? 2 : 0);
-  *bits = c->headBitsHost + ((at.half ? (size_t)c->wide.maxReads : 0) + (size_t)at.slot) * wideHeadWords(c->wide);
+  *bits = c->wide.headHost.p + ((at.half ? (size_t)c->wide.maxReads : 0) + (size_t)at.slot) * wideHeadWords(c->wide);
   return 1;
 }
 
@@ -2603,7 +2607,7 @@ int t4_add_query_last_cands(t4_ctx *c, const t4_cand **pool, const int32_t **bas
   if (!c || !c->aqOutHost) return T4_ERR_ARG;
   const AqCall &q = c->aq;
   static_assert(sizeof(t4_cand) == sizeof(T4Cand) && sizeof(T4Cand) == 24 && T4_QUERY_STATS == T4_QSTATS, "candidate record layout");
-  if (pool) *pool = q.wantCands ? (const t4_cand *)c->candPool : nullptr;
+  if (pool) *pool = q.wantCands ? (const t4_cand *)c->candPool.p : nullptr;
   if (base) *base = q.hdr.candBase.host(c);
   if (cnt) *cnt = q.wantCands ? q.hdr.candCnt.host(c) : nullptr;
   if (stats8) *stats8 = q.hdr.stats8.host(c);
@@ -2640,23 +2644,24 @@ struct t4_cellstore {
   struct Slot { unsigned char *base = nullptr; size_t cap = 0, imgBytes = 0; bool live = false; bool pending = false; };
   std::vector<Slot> slots;
   std::vector<int> freeIds;
-  std::vector<unsigned char *> chunks;
+  std::vector<DevBuf<unsigned char>> chunks;   // (Slot::base and freeBySize point into these)
   size_t chunkUsed = 0;
   std::map<size_t, std::vector<unsigned char *>> freeBySize;
-  T4IndexView *dViews = nullptr;
+  DevBuf<T4IndexView> dViews;
   int viewCap = 0;
-  unsigned char *stHost = nullptr, *stDev = nullptr;   // staging of the images rebuilt since the last flush
+  PinnedBuf<unsigned char> stHost;   // staging of the images rebuilt since the last flush
+  DevBuf<unsigned char> stDev;
   size_t stCap = 0, stUsed = 0;
   std::vector<T4CopyDesc> descs;
-  T4CopyDesc *dDescs = nullptr;
+  DevBuf<unsigned char> dDescs;
   size_t descCap = 0;   // bytes: the descriptors of a flush and, behind them, its table builds travel in one copy
   std::vector<T4TableBuild> builds;   // tables of the compact images of this flush (t4_cellstore_stage_compact)
   std::vector<int> buildSlots;        // ... and the slot each belongs to, for the error text
   std::vector<unsigned char> ctlHost;
-  int *dBuildErr = nullptr, *hBuildErr = nullptr;   // 0, or 1 + the number of a build that met a duplicate key (device word, pinned copy)
+  DevBuf<int> dBuildErr; PinnedBuf<int> hBuildErr;   // 0, or 1 + the number of a build that met a duplicate key (device word, pinned copy)
   int64_t imagesBuilt = 0, keysShipped = 0, tableBytesBuilt = 0;
   std::vector<T4BytePatch> patches;
-  T4BytePatch *dPatches = nullptr;
+  DevBuf<T4BytePatch> dPatches;
   size_t patchCap = 0;
   int64_t bytesPatched = 0;
   int64_t bytesStaged = 0;
@@ -2671,11 +2676,11 @@ int cellAlloc(t4_cellstore *cs, size_t cap, unsigned char **out) {
   if (it != cs->freeBySize.end() && !it->second.empty()) { *out = it->second.back(); it->second.pop_back(); return T4_OK; }
   if (cap > t4_cellstore::CHUNK) return fail(cs->ctx, T4_ERR_UNSUPPORTED, "a per-barcode set image of %zu bytes exceeds the arena chunk", cap);
   if (cs->chunks.empty() || cs->chunkUsed + cap > t4_cellstore::CHUNK) {
-    unsigned char *p = nullptr;
-    HIPCHK(cs->ctx, hipMalloc(&p, t4_cellstore::CHUNK));
-    cs->chunks.push_back(p); cs->chunkUsed = 0;
+    DevBuf<unsigned char> chunk;
+    if (int r = chunk.alloc(cs->ctx, t4_cellstore::CHUNK)) return r;
+    cs->chunks.push_back(std::move(chunk)); cs->chunkUsed = 0;
   }
-  *out = cs->chunks.back() + cs->chunkUsed;
+  *out = cs->chunks.back().p + cs->chunkUsed;
   cs->chunkUsed += cap;
   return T4_OK;
 }
@@ -2683,28 +2688,29 @@ int cellStagingReserve(t4_cellstore *cs, size_t more) {
   if (cs->stUsed + more <= cs->stCap) return T4_OK;
   size_t ncap = cs->stCap ? cs->stCap : ((size_t)4 << 20);
   while (ncap < cs->stUsed + more) ncap *= 2;
-  unsigned char *nh = nullptr, *nd = nullptr;
-  HIPCHK(cs->ctx, hipHostMalloc(&nh, ncap, hipHostMallocDefault));
-  HIPCHK(cs->ctx, hipMalloc(&nd, ncap));
-  if (cs->stUsed) memcpy(nh, cs->stHost, cs->stUsed);
-  if (cs->stHost) (void)hipHostFree(cs->stHost);
-  if (cs->stDev) { (void)hipStreamSynchronize(cs->ctx->stream); (void)hipFree(cs->stDev); }
-  cs->stHost = nh; cs->stDev = nd; cs->stCap = ncap;
+  PinnedBuf<unsigned char> nh;   // (what is staged already is kept: the old pair stays until the new one stands)
+  DevBuf<unsigned char> nd;
+  int r;
+  if ((r = nh.alloc(cs->ctx, ncap, hipHostMallocDefault)) || (r = nd.alloc(cs->ctx, ncap))) return r;
+  if (cs->stUsed) memcpy(nh.p, cs->stHost.p, cs->stUsed);
+  if (cs->stDev) (void)hipStreamSynchronize(cs->ctx->stream);
+  cs->stHost.swap(nh); cs->stDev.swap(nd); cs->stCap = ncap;
   return T4_OK;
 }
 int cellFlushPatches(t4_cellstore *cs) {
   if (cs->patches.empty()) return T4_OK;
   t4_ctx *c = cs->ctx;
   if (cs->patches.size() > cs->patchCap) {
-    if (cs->dPatches) { (void)hipStreamSynchronize(c->stream); (void)hipFree(cs->dPatches); cs->dPatches = nullptr; }
+    if (cs->dPatches) (void)hipStreamSynchronize(c->stream);
+    cs->patchCap = 0;
+    if (int r = cs->dPatches.alloc(c, cs->patches.size() * 2)) return r;
     cs->patchCap = cs->patches.size() * 2;
-    HIPCHK(c, hipMalloc(&cs->dPatches, sizeof(T4BytePatch) * cs->patchCap));
   }
   HIPCHK(c, hipMemcpyAsync(cs->dPatches, cs->patches.data(), sizeof(T4BytePatch) * cs->patches.size(), hipMemcpyHostToDevice, c->stream));
   const int n = (int)cs->patches.size();
   int grid = (n + 255) / 256;
   if (grid > c->cus * 4) grid = c->cus * 4;
-  hipLaunchKernelGGL(t4k::patchKernel, dim3(grid), dim3(256), 0, c->stream, (const T4BytePatch *)cs->dPatches, n);
+  hipLaunchKernelGGL(t4k::patchKernel, dim3(grid), dim3(256), 0, c->stream, (const T4BytePatch *)cs->dPatches.p, n);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));   // the host vector is reused
   cs->bytesPatched += n;
@@ -2716,11 +2722,10 @@ int cellFlush(t4_cellstore *cs) {
   t4_ctx *c = cs->ctx;
   const size_t descBytes = (sizeof(T4CopyDesc) * cs->descs.size() + 15) & ~(size_t)15, buildBytes = sizeof(T4TableBuild) * cs->builds.size();
   if (descBytes + buildBytes > cs->descCap) {
-    if (cs->dDescs) { (void)hipStreamSynchronize(c->stream); (void)hipFree(cs->dDescs); cs->dDescs = nullptr; }
+    if (cs->dDescs) (void)hipStreamSynchronize(c->stream);
+    cs->descCap = 0;
+    if (int r = cs->dDescs.alloc(c, (descBytes + buildBytes) * 2)) return r;
     cs->descCap = (descBytes + buildBytes) * 2;
-    unsigned char *p = nullptr;
-    HIPCHK(c, hipMalloc(&p, cs->descCap));
-    cs->dDescs = (T4CopyDesc *)p;
   }
   const unsigned char *ctl = (const unsigned char *)cs->descs.data();
   if (buildBytes) {
@@ -2732,21 +2737,22 @@ int cellFlush(t4_cellstore *cs) {
   HIPCHK(c, hipMemcpyAsync(cs->stDev, cs->stHost, cs->stUsed, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(cs->dDescs, ctl, buildBytes ? descBytes + buildBytes : sizeof(T4CopyDesc) * cs->descs.size(), hipMemcpyHostToDevice, c->stream));
   if (buildBytes) {   // the tables first, then the rest of the images: the two write disjoint bytes of a slot
-    if (!cs->hBuildErr) HIPCHK(c, hipHostMalloc(&cs->hBuildErr, sizeof(int), hipHostMallocDefault));
+    int r;
+    if (!cs->hBuildErr && (r = cs->hBuildErr.alloc(c, 1, hipHostMallocDefault))) return r;
     if (!cs->dBuildErr) {
-      HIPCHK(c, hipMalloc(&cs->dBuildErr, sizeof(int)));
+      if ((r = cs->dBuildErr.alloc(c, 1))) return r;
       HIPCHK(c, hipMemsetAsync(cs->dBuildErr, 0, sizeof(int), c->stream));
     }
     int bgrid = (int)cs->builds.size();
     if (bgrid > c->cus * 8) bgrid = c->cus * 8;
-    hipLaunchKernelGGL(t4k::cellTableBuildKernel, dim3(bgrid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev,
-                       (const T4TableBuild *)((const unsigned char *)cs->dDescs + descBytes), (int)cs->builds.size(), cs->dBuildErr);
+    hipLaunchKernelGGL(t4k::cellTableBuildKernel, dim3(bgrid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev.p,
+                       (const T4TableBuild *)(cs->dDescs.p + descBytes), (int)cs->builds.size(), cs->dBuildErr.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(cs->hBuildErr, cs->dBuildErr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   }
   int grid = (int)cs->descs.size();
   if (grid > c->cus * 8) grid = c->cus * 8;
-  hipLaunchKernelGGL(t4k::scatterKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev, (const T4CopyDesc *)cs->dDescs, (int)cs->descs.size());
+  hipLaunchKernelGGL(t4k::scatterKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev.p, (const T4CopyDesc *)cs->dDescs.p, (int)cs->descs.size());
   HIPCHK(c, hipGetLastError());
   // the pageable descriptor vector and the pinned staging are reused by the next stage() calls
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2755,7 +2761,7 @@ int cellFlush(t4_cellstore *cs) {
   if (buildBytes) {
     cs->imagesBuilt += (int64_t)cs->builds.size();
     for (const T4TableBuild &tb : cs->builds) { cs->keysShipped += (int64_t)tb.nKeys; cs->tableBytesBuilt += (int64_t)(sizeof(T4HashEntC) * tb.tableSlots); }
-    const int e = *cs->hBuildErr;
+    const int e = *cs->hBuildErr.p;
     if (e) {
       badSlot = (e >= 1 && e <= (int)cs->buildSlots.size()) ? cs->buildSlots[e - 1] : -2;
       (void)hipMemsetAsync(cs->dBuildErr, 0, sizeof(int), c->stream);
@@ -2788,14 +2794,6 @@ void t4_cellstore_destroy(t4_cellstore *cs) {
   if (!cs) return;
   (void)hipSetDevice(cs->ctx->device);
   (void)hipStreamSynchronize(cs->ctx->stream);
-  for (unsigned char *p : cs->chunks) (void)hipFree(p);
-  if (cs->dViews) (void)hipFree(cs->dViews);
-  if (cs->stDev) (void)hipFree(cs->stDev);
-  if (cs->stHost) (void)hipHostFree(cs->stHost);
-  if (cs->dDescs) (void)hipFree(cs->dDescs);
-  if (cs->dBuildErr) (void)hipFree(cs->dBuildErr);
-  if (cs->hBuildErr) (void)hipHostFree(cs->hBuildErr);
-  if (cs->dPatches) (void)hipFree(cs->dPatches);
   delete cs;
 }
 int t4_cellstore_set_params(t4_cellstore *cs, int hit_len_required, int radius, double novel_sim) {
@@ -2851,15 +2849,9 @@ int t4_cellstore_prepare(t4_cellstore *cs, int max_slot, size_t bytes) {
   if (max_slot >= cs->viewCap) {
     int ncap = cs->viewCap ? cs->viewCap : 1024;
     while (ncap <= max_slot) ncap *= 2;
-    T4IndexView *nv = nullptr;
-    HIPCHK(c, hipMalloc(&nv, sizeof(T4IndexView) * (size_t)ncap));
     if ((r = cellFlush(cs))) return r;   // pending descriptors may point into the old array
-    if (cs->dViews) {
-      HIPCHK(c, hipMemcpyAsync(nv, cs->dViews, sizeof(T4IndexView) * (size_t)cs->viewCap, hipMemcpyDeviceToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      (void)hipFree(cs->dViews);
-    }
-    cs->dViews = nv; cs->viewCap = ncap;
+    if ((r = cs->dViews.growKeep(c, cs->viewCap, ncap))) return r;
+    cs->viewCap = ncap;
   }
   return cellStagingReserve(cs, bytes);
 }
@@ -2910,14 +2902,14 @@ int cellStage(t4_cellstore *cs, bool compact, int slot, int barcode, int nseq, c
       while (cap < blobBytes + blobBytes / 2) cap <<= 1;
       sl.base = nullptr; sl.cap = 0;
       unsigned char *p = nullptr;
-      if ((r = cellAlloc(cs, cap, &p))) return r;
+      if ((r = cellAlloc(cs, cap, &p))) { sl.pending = false; return r; }   // (nothing of it is staged: the caller may stage the slot again)
       sl.base = p; sl.cap = cap;
     }
     slotBase = sl.base; sl.imgBytes = blobBytes;
     if (slot >= cs->viewCap || cs->stUsed + stagedBlob + viewBytes > cs->stCap)
       return fail(c, T4_ERR_STATE, "t4_cellstore_stage without a sufficient t4_cellstore_prepare (slot %d, %zu bytes)", slot, stagedBlob + viewBytes);
     stOff = cs->stUsed;
-    b = cs->stHost + stOff;
+    b = cs->stHost.p + stOff;
     T4CopyDesc d0; d0.srcOff = stOff; d0.dst = slotBase; d0.bytes = blobBytes;
     if (compact) {
       d0.srcOff = stOff + headBytes; d0.dst = slotBase + oPost; d0.bytes = blobBytes - oPost;
