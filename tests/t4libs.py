@@ -405,6 +405,19 @@ class RefSeqSet:
         if consider_barcode:
             self.lib.ref_set_consider_barcode(self.h, 1)
 
+    SHALLOW_PATH = os.path.join(ROOT, "oracle", "_ref", "libt4refshallow.so")
+
+    @classmethod
+    def shallow_available(cls):
+        return Ref.available() and os.path.exists(cls.SHALLOW_PATH)
+
+    def release_shallow_contigs(self, min_cov):
+        """SeqSet::ReleaseShallowContigs, from a library of its own (oracle/ref_shallow_probe.cpp)"""
+        lib = C.CDLL(self.SHALLOW_PATH)
+        lib.refx_release_shallow_contigs.argtypes = [C.c_void_p, C.c_int]
+        lib.refx_release_shallow_contigs.restype = None
+        lib.refx_release_shallow_contigs(self.h, min_cov)
+
     def release_finished_barcode(self, barcode, total=1):
         self.lib.ref_release_finished_barcode(self.h, barcode, total)
 

@@ -671,6 +671,26 @@ class LiveImage:
 
     def add(self, name, cons, weights=None):
         idx = len(self.seqs)
+        self.seqs.append(None)
+        self._place(idx, name, cons, weights)
+        return idx
+
+    def replace(self, idx, cons, weights=None):
+        """contig idx gets another consensus: every posting of it leaves its list (the list's last entry takes the place; a list may
+        reach cnt 0, its key stays in the table), the new consensus is indexed and stored at a fresh place of the base arena"""
+        for code, e in self.keys.items():
+            t = 0
+            while t < e[2]:
+                if self.post[e[1] + t][0] == idx:
+                    e[2] -= 1
+                    self.post[e[1] + t] = self.post[e[1] + e[2]]
+                    self.dirty_post.add(e[1] + t)
+                    self.dirty_keys.add(code)
+                else:
+                    t += 1
+        self._place(idx, self.seqs[idx][3], cons, weights)
+
+    def _place(self, idx, name, cons, weights):
         num = {"A": 0, "C": 1, "G": 2, "T": 3}
         code, prev, invalid = 0, 0, -1
         mask = (1 << (2 * self.k)) - 1
@@ -696,12 +716,12 @@ class LiveImage:
             sm = sum(w)
             pw.append((16 if sm == 0 else 0) | sum((1 << x) for x in range(4) if sm < 3 * w[x]))
         pw.append(16)
-        self.seqs.append((self.bases_used, cons, bytes(pw), name))
+        self.seqs[idx] = (self.bases_used, cons, bytes(pw), name)
         self.bases_used += len(cons) + 1 + 17   # room nobody uses: arenas need not be dense
         self.dirty_seq.add(idx)
-        return idx
 
-    def flush(self, ix):
+    def flush(self, ix, max_seq_len=None):
+        """max_seq_len: what the caller tells the image about its longest contig (the true maximum unless given)"""
         keys = self.keys if self.rebuilt else {c: self.keys[c] for c in self.dirty_keys}
         slots = [(e[0], c, e[1], e[2]) for c, e in keys.items()]
         runs, cur = [], None
@@ -714,7 +734,7 @@ class LiveImage:
         seqs = [(i, self.seqs[i][0], len(self.seqs[i][1]), -1, self.seqs[i][3]) for i in sorted(self.dirty_seq)]
         bases = [(self.seqs[i][0], self.seqs[i][1].encode() + b"\0", self.seqs[i][2]) for i in sorted(self.dirty_seq)]
         ix.apply_delta(self.slots, 1 if self.rebuilt else 0, len(self.post) + 8, self.bases_used + 8, len(self.seqs) + 4, len(self.seqs),
-                       max(len(x[1]) for x in self.seqs), slots, [(r[0], r[1]) for r in runs], seqs, bases)
+                       max(len(x[1]) for x in self.seqs) if max_seq_len is None else max_seq_len, slots, [(r[0], r[1]) for r in runs], seqs, bases)
         self.dirty_keys, self.dirty_post, self.dirty_seq, self.rebuilt = set(), set(), set(), False
 
 

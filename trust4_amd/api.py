@@ -370,6 +370,9 @@ class Assembler:
     def release_finished_barcode(self, barcode, contig_min_cov=0):
         self.eng.check(self.eng.lib.t4_assembler_release_finished_barcode(self.h, barcode, contig_min_cov))
 
+    def release_shallow_contigs(self, min_cov):
+        self.eng.check(self.eng.lib.t4_assembler_release_shallow_contigs(self.h, min_cov))
+
     def _ret(self, r):
         if r < -50:
             raise T4Error(r + 100, self.eng.lib.t4_last_error(self.eng.h).decode())

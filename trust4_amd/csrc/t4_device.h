@@ -52,7 +52,7 @@ struct T4HashEnt {           // open-addressing slot of the (code, bucket) -> po
 };
 
 struct alignas(16) T4IndexView {   // 128 bytes: per-barcode views are scattered in 16-byte units
-  int k, nseq, direct /* 0 htab, 1 table, 2 ctab */, considerBarcode;
+  int k, nseq, direct /* 0 htab, 1 table, 2 ctab of a per-barcode image, 3 ctab of a live set (t4_index_apply_delta) */, considerBarcode;
   unsigned long long hashMask;
   const uint2 *table;        // direct-addressed [4^k] {start,cnt} (k <= 12, no barcode)
   const T4HashEnt *htab;

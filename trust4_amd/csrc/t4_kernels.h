@@ -747,6 +747,10 @@ struct WaveMem {
   const unsigned *pkRow, *nmRow;   // the read's packed words (global), set by loadSegment
   int segAbs, segLen;              // position of the current segment inside the read
 };
+// The seed stage keeps the posting-list start of every k-mer position of both strands in the overlap array (posStart: one word per
+// position; the array is dead until the first overlap is written). The 64 records of the smallest tier hold 640 words: a read of more
+// than 328 bases at k = 9 has more positions and is handed on to the next tier, whose 128 records hold those of every read.
+__device__ __forceinline__ bool posStartFits(const WaveMem &wm, int nk) { return 2 * nk <= wm.maxOv * (int)(sizeof(OvRec) / sizeof(unsigned)); }
 
 struct WaveState { // wave-uniform scalars kept in LDS
   int ovCount, candCount, jobCount, overflow, unsupported, finCount, nContig, sortBad;
@@ -2477,6 +2481,7 @@ __device__ int seedChainPass(const T4IndexView &ix, WaveMem &wm, WaveState *ws, 
   unsigned *posStart = (unsigned *)wm.ov;   // dead before the first overlap record is written
   unsigned *posPref = wm.pairs;             // dead before the first pair is written
   const int nk = segLen - ix.k + 1;
+  if (!posStartFits(wm, nk)) return -1;     // (wave-uniform) the next tier's overlap array holds the positions of every read
   if (lane == 0) ws->ovCount = 0;
   PHASE_MARK(ws, 1);
   int H = NOVEL ? seedPositionsNovel(ix, wm, segLen, strandArg, barcode, allowTotalSkip, posStart, posPref, ws->red, wm.keys, ws)
@@ -3856,6 +3861,7 @@ __device__ bool processRead(const T4IndexView &ix, const T4BatchView &bv, const 
       loadSegment(bv, r, 0, len, wm);
       unsigned *posStart = (unsigned *)wm.ov, *posPref = wm.pairs;
       const int nk = len - ix.k + 1;
+      if (!posStartFits(wm, nk)) return false;
       int H = seedPositions(ix, wm, len, 0, -1, false, posStart, posPref, ws->red);
       if (H > wm.hitLimit) return false;
       hitTotal += (unsigned long long)H;
