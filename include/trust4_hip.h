@@ -381,6 +381,20 @@ int t4_cellset_counters(const t4_cellset *cs, int64_t *query_batches, int64_t *r
  * min(n, 4) of: images whose table was built on the device; key records shipped for them; table bytes written on the device
  * (16 per slot, summed over those images); bytes staged over PCIe (== bytes_staged of t4_cellset_counters). */
 int t4_cellset_image_stats(const t4_cellset *cs, int64_t *out, int n);
+/* The form a cell's image travels in. T4_CELL_IMAGE_COMPACT (the default) is the one described above. T4_CELL_IMAGE_INDEXED ships
+ * no index at all: every posting (contig, offset) of a cell's index has the code of the contig's k-mer at that offset, and nothing
+ * a query returns depends on the order inside a posting list, so the image travels as its contigs plus one byte per consensus
+ * position -- the number of postings the index holds there -- and the device builds the hash table and the posting lists in the
+ * cell's arena slot from them. The device image differs from the compact form's only in where keys and postings lie; queries
+ * answer the same. A cell in which one offset collects more than 255 postings goes back to the compact form for good.
+ * To be called before the first t4_cellset_prefetch (T4_ERR_STATE afterwards); T4_ERR_ARG for any other form. */
+enum { T4_CELL_IMAGE_COMPACT = 0, T4_CELL_IMAGE_INDEXED = 1 };
+int t4_cellset_set_image_form(t4_cellset *cs, int form);
+/* The indexed form's own counters, the first min(n, 6) of: images whose table and postings were built on the device; count bytes
+ * shipped for them; postings written on the device; table bytes written on the device (16 per slot); cells that went back to the
+ * compact form (a count past 255); images whose counts were checked against the host's index (test builds only, else 0).
+ * t4_cellset_image_stats keeps its meaning: its first three values count the compact images alone, its fourth every staged byte. */
+int t4_cellset_indexed_stats(const t4_cellset *cs, int64_t *out, int n);
 
 /* ---- k-mer counts of the read set ------------------------------------------------ */
 /* KmerCount (KmerCount.hpp): counts of the canonical k-mers of the reads (main.cpp:905-915 counts 21-mers of every read that

@@ -2658,8 +2658,13 @@ struct t4_cellstore {
   std::vector<T4TableBuild> builds;   // tables of the compact images of this flush (t4_cellstore_stage_compact)
   std::vector<int> buildSlots;        // ... and the slot each belongs to, for the error text
   std::vector<unsigned char> ctlHost;
-  DevBuf<int> dBuildErr; PinnedBuf<int> hBuildErr;   // 0, or 1 + the number of a build that met a duplicate key (device word, pinned copy)
+  std::vector<T4IndexBuild> ibuilds;   // tables and postings of the indexed images of this flush (t4_cellstore_stage_indexed)
+  std::vector<int> ibuildSlots;
+  // four words (device, pinned copy). [0]: 0, or 1 + the number of a table build that met a duplicate key; [2], [3]: 0, or 1 + the
+  // number of an index build that gave up, and why (T4_IDXERR_*)
+  DevBuf<int> dBuildErr; PinnedBuf<int> hBuildErr;
   int64_t imagesBuilt = 0, keysShipped = 0, tableBytesBuilt = 0;
+  int64_t imagesIndexed = 0, countBytesShipped = 0, postingsIndexed = 0, tableBytesIndexed = 0;
   std::vector<T4BytePatch> patches;
   DevBuf<T4BytePatch> dPatches;
   size_t patchCap = 0;
@@ -2720,7 +2725,8 @@ int cellFlushPatches(t4_cellstore *cs) {
 int cellFlush(t4_cellstore *cs) {
   if (cs->descs.empty()) return cellFlushPatches(cs);
   t4_ctx *c = cs->ctx;
-  const size_t descBytes = (sizeof(T4CopyDesc) * cs->descs.size() + 15) & ~(size_t)15, buildBytes = sizeof(T4TableBuild) * cs->builds.size();
+  const size_t descBytes = (sizeof(T4CopyDesc) * cs->descs.size() + 15) & ~(size_t)15, tblBytes = sizeof(T4TableBuild) * cs->builds.size(),
+               buildBytes = tblBytes + sizeof(T4IndexBuild) * cs->ibuilds.size();
   if (descBytes + buildBytes > cs->descCap) {
     if (cs->dDescs) (void)hipStreamSynchronize(c->stream);
     cs->descCap = 0;
@@ -2731,24 +2737,34 @@ int cellFlush(t4_cellstore *cs) {
   if (buildBytes) {
     cs->ctlHost.resize(descBytes + buildBytes);
     memcpy(cs->ctlHost.data(), cs->descs.data(), sizeof(T4CopyDesc) * cs->descs.size());
-    memcpy(cs->ctlHost.data() + descBytes, cs->builds.data(), buildBytes);
+    if (tblBytes) memcpy(cs->ctlHost.data() + descBytes, cs->builds.data(), tblBytes);
+    if (buildBytes > tblBytes) memcpy(cs->ctlHost.data() + descBytes + tblBytes, cs->ibuilds.data(), buildBytes - tblBytes);
     ctl = cs->ctlHost.data();
   }
   HIPCHK(c, hipMemcpyAsync(cs->stDev, cs->stHost, cs->stUsed, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(cs->dDescs, ctl, buildBytes ? descBytes + buildBytes : sizeof(T4CopyDesc) * cs->descs.size(), hipMemcpyHostToDevice, c->stream));
-  if (buildBytes) {   // the tables first, then the rest of the images: the two write disjoint bytes of a slot
+  if (buildBytes) {   // the tables (and the postings of the indexed images) first, then the rest of the images: they write disjoint bytes of a slot
     int r;
-    if (!cs->hBuildErr && (r = cs->hBuildErr.alloc(c, 1, hipHostMallocDefault))) return r;
+    if (!cs->hBuildErr && (r = cs->hBuildErr.alloc(c, 4, hipHostMallocDefault))) return r;
     if (!cs->dBuildErr) {
-      if ((r = cs->dBuildErr.alloc(c, 1))) return r;
-      HIPCHK(c, hipMemsetAsync(cs->dBuildErr, 0, sizeof(int), c->stream));
+      if ((r = cs->dBuildErr.alloc(c, 4))) return r;
+      HIPCHK(c, hipMemsetAsync(cs->dBuildErr, 0, sizeof(int) * 4, c->stream));
     }
-    int bgrid = (int)cs->builds.size();
-    if (bgrid > c->cus * 8) bgrid = c->cus * 8;
-    hipLaunchKernelGGL(t4k::cellTableBuildKernel, dim3(bgrid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev.p,
-                       (const T4TableBuild *)(cs->dDescs.p + descBytes), (int)cs->builds.size(), cs->dBuildErr.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(cs->hBuildErr, cs->dBuildErr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (tblBytes) {
+      int bgrid = (int)cs->builds.size();
+      if (bgrid > c->cus * 8) bgrid = c->cus * 8;
+      hipLaunchKernelGGL(t4k::cellTableBuildKernel, dim3(bgrid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev.p,
+                         (const T4TableBuild *)(cs->dDescs.p + descBytes), (int)cs->builds.size(), cs->dBuildErr.p);
+      HIPCHK(c, hipGetLastError());
+    }
+    if (buildBytes > tblBytes) {
+      int bgrid = (int)cs->ibuilds.size();
+      if (bgrid > c->cus * 8) bgrid = c->cus * 8;
+      hipLaunchKernelGGL(t4k::cellIndexBuildKernel, dim3(bgrid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev.p,
+                         (const T4IndexBuild *)(cs->dDescs.p + descBytes + tblBytes), (int)cs->ibuilds.size(), cs->dBuildErr.p + 2);
+      HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(cs->hBuildErr, cs->dBuildErr, sizeof(int) * 4, hipMemcpyDeviceToHost, c->stream));
   }
   int grid = (int)cs->descs.size();
   if (grid > c->cus * 8) grid = c->cus * 8;
@@ -2757,22 +2773,34 @@ int cellFlush(t4_cellstore *cs) {
   // the pageable descriptor vector and the pinned staging are reused by the next stage() calls
   HIPCHK(c, hipStreamSynchronize(c->stream));
   cs->bytesStaged += (int64_t)cs->stUsed;
-  int badSlot = -1;
+  int badSlot = -1, badIndexed = -1, why = 0;
   if (buildBytes) {
     cs->imagesBuilt += (int64_t)cs->builds.size();
     for (const T4TableBuild &tb : cs->builds) { cs->keysShipped += (int64_t)tb.nKeys; cs->tableBytesBuilt += (int64_t)(sizeof(T4HashEntC) * tb.tableSlots); }
-    const int e = *cs->hBuildErr.p;
-    if (e) {
-      badSlot = (e >= 1 && e <= (int)cs->buildSlots.size()) ? cs->buildSlots[e - 1] : -2;
-      (void)hipMemsetAsync(cs->dBuildErr, 0, sizeof(int), c->stream);
+    cs->imagesIndexed += (int64_t)cs->ibuilds.size();
+    for (const T4IndexBuild &ib : cs->ibuilds) {
+      cs->countBytesShipped += (int64_t)((ib.consBytes + 15u) & ~15u); cs->postingsIndexed += (int64_t)ib.npost;
+      cs->tableBytesIndexed += (int64_t)(sizeof(T4HashEntC) * ib.tableSlots);
+    }
+    const int e = cs->hBuildErr.p[0], ei = cs->hBuildErr.p[2];
+    if (e) badSlot = (e >= 1 && e <= (int)cs->buildSlots.size()) ? cs->buildSlots[e - 1] : -2;
+    if (ei) { badIndexed = (ei >= 1 && ei <= (int)cs->ibuildSlots.size()) ? cs->ibuildSlots[ei - 1] : -2; why = cs->hBuildErr.p[3]; }
+    if (e || ei) {
+      (void)hipMemsetAsync(cs->dBuildErr, 0, sizeof(int) * 4, c->stream);
       (void)hipStreamSynchronize(c->stream);
     }
   }
-  cs->descs.clear(); cs->builds.clear(); cs->buildSlots.clear(); cs->stUsed = 0;
+  cs->descs.clear(); cs->builds.clear(); cs->buildSlots.clear(); cs->ibuilds.clear(); cs->ibuildSlots.clear(); cs->stUsed = 0;
   for (t4_cellstore::Slot &sl : cs->slots) sl.pending = false;
   if (badSlot != -1) {   // the store goes on; that slot's table is incomplete until its cell is staged again
     (void)cellFlushPatches(cs);
     return fail(c, T4_ERR_ARG, "the key records of the image of slot %d hold the same code twice", badSlot);
+  }
+  if (badIndexed != -1) {   // likewise: that slot's table and postings are incomplete until its cell is staged again
+    (void)cellFlushPatches(cs);
+    return fail(c, T4_ERR_ARG, "the index of the image of slot %d could not be built from its contigs: %s", badIndexed,
+                why == T4_IDXERR_KMER ? "a counted offset has no k-mer of ACGT" : why == T4_IDXERR_FULL ? "the table of nkeys keys is too small for its distinct k-mers"
+                                                                                 : "the counts do not add up to npost");
   }
   return cellFlushPatches(cs);
 }
@@ -2832,6 +2860,11 @@ size_t cellStagedBytes(size_t tableSlots, int nseq, int64_t nkeys, int64_t npost
 size_t t4_cellstore_image_bytes(int nseq, int64_t nkeys, int64_t npost, int64_t cons_bytes) {
   return cellStagedBytes(0, nseq, nkeys, npost, cons_bytes);
 }
+// t4_cellstore_stage_indexed: one count byte per consensus byte, the image from its sequence records on, the view
+size_t t4_cellstore_indexed_image_bytes(int nseq, int64_t cons_bytes) {
+  auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  return al16((size_t)cons_bytes) + cellStagedBytes(0, nseq, 0, 0, cons_bytes);
+}
 // t4_cellstore_stage: the whole image with its table, the view (never less than the compact form of the same cell)
 size_t t4_cellstore_full_image_bytes(int nseq, int64_t nkeys, int64_t npost, int64_t cons_bytes) {
   size_t sz = 64;
@@ -2861,9 +2894,12 @@ int t4_cellstore_prepare(t4_cellstore *cs, int max_slot, size_t bytes) {
 namespace {
 // One cell's image into staging. compact: the table travels as the (code, start, cnt) records of its keys and is built in the slot
 // by cellTableBuildKernel; everything from the postings on is staged, and lands in the slot, as in the full form.
+// indexed (t4_cellstore_stage_indexed): neither table nor postings travel; npostIn postings are announced, postCnt[i][o] of them at
+// offset o of contig i (postCntLen[i] bytes, the rest zeros), and cellIndexBuildKernel writes both in the slot from the staged contigs.
 int cellStage(t4_cellstore *cs, bool compact, int slot, int barcode, int nseq, const char *const *names, const char *const *cons,
               const int32_t *const *pw, int64_t nkeys64, const uint64_t *keyCode, const int32_t *keyBucket, const int32_t *keyCnt,
-              const int32_t *postIn, int64_t *pwOffsetInImage, const int32_t *seqBarcodes) {
+              const int32_t *postIn, int64_t *pwOffsetInImage, const int32_t *seqBarcodes, bool indexed = false, int64_t npostIn = 0,
+              const uint8_t *const *postCnt = nullptr, const int32_t *postCntLen = nullptr) {
   if (!cs || slot < 0 || slot >= (int)cs->slots.size() || !cs->slots[slot].live || nseq < 0 || nkeys64 < 0) return T4_ERR_ARG;
   t4_ctx *c = cs->ctx;
   (void)hipSetDevice(c->device);
@@ -2871,7 +2907,22 @@ int cellStage(t4_cellstore *cs, bool compact, int slot, int barcode, int nseq, c
   const size_t nkeys = (size_t)nkeys64;
   int64_t npost = 0;
   size_t nLive = 0;   // keys that own postings: the entries of the table
-  for (size_t i = 0; i < nkeys; ++i) { npost += keyCnt[i]; if (keyCnt[i] > 0) ++nLive; }
+  if (!indexed) for (size_t i = 0; i < nkeys; ++i) { npost += keyCnt[i]; if (keyCnt[i] > 0) ++nLive; }
+  else {   // refused here, before anything is queued: counts that cannot be postings of these contigs, or that are not npost of them
+    if (npostIn < 0 || npostIn > 0xFFFFFFFFll || (npostIn > 0 && nkeys == 0)) return fail(c, T4_ERR_ARG, "an indexed image of %lld postings with %lld keys", (long long)npostIn, (long long)nkeys64);
+    int64_t sum = 0;
+    for (int i = 0; i < nseq && postCnt; ++i) {
+      if (!postCnt[i]) continue;
+      const int l = (int)strlen(cons[i]), n = postCntLen ? postCntLen[i] : l;
+      for (int o = 0; o < n; ++o) {
+        if (!postCnt[i][o]) continue;
+        if (o + cs->k > l) return fail(c, T4_ERR_ARG, "postings counted at offset %d of contig %d, which has %d bases (k = %d)", o, i, l, cs->k);
+        sum += postCnt[i][o];
+      }
+    }
+    if (sum != npostIn) return fail(c, T4_ERR_ARG, "the counts of the image of slot %d add up to %lld postings, %lld were announced", slot, (long long)sum, (long long)npostIn);
+    npost = npostIn;
+  }
   size_t sz = 64;
   while (2 * sz < 3 * nkeys + 2) sz <<= 1;   // load factor <= 2/3
   size_t consBytes = 0, pwCount = 0;
@@ -2886,8 +2937,9 @@ int cellStage(t4_cellstore *cs, bool compact, int slot, int barcode, int nseq, c
                blobBytes = al16(oCons + consBytes + 16);
   int r;
   const size_t viewBytes = al16(sizeof(T4IndexView));
-  // staged: [key records | table] [oPost .. blobBytes of the image] [view]
-  const size_t headBytes = compact ? sizeof(T4HashEntC) * nLive : oPost, stagedBlob = headBytes + (blobBytes - oPost);
+  // staged: [key records | table] [oPost .. blobBytes of the image] [view]; indexed: [count bytes] [oSeq .. blobBytes of the image] [view]
+  const size_t tailFrom = indexed ? oSeq : oPost;
+  const size_t headBytes = indexed ? al16(consBytes) : compact ? sizeof(T4HashEntC) * nLive : oPost, stagedBlob = headBytes + (blobBytes - tailFrom);
   unsigned char *b = nullptr, *slotBase = nullptr;
   size_t stOff = 0;
   {
@@ -2916,18 +2968,35 @@ int cellStage(t4_cellstore *cs, bool compact, int slot, int barcode, int nseq, c
       T4TableBuild tb; tb.table = (T4HashEntC *)(slotBase + oHt); tb.tableSlots = sz; tb.srcOff = stOff; tb.nKeys = nLive;
       cs->builds.push_back(tb); cs->buildSlots.push_back(slot);
     }
+    if (indexed) {
+      d0.srcOff = stOff + headBytes; d0.dst = slotBase + oSeq; d0.bytes = blobBytes - oSeq;
+      T4IndexBuild ib; ib.table = (T4HashEntC *)(slotBase + oHt); ib.post = (int2 *)(slotBase + oPost); ib.tableSlots = sz;
+      ib.cntOff = stOff; ib.seqOff = stOff + headBytes; ib.consOff = stOff + headBytes + (oCons - oSeq);
+      ib.consBytes = (unsigned)consBytes; ib.npost = (unsigned)npost; ib.nseq = nseq; ib.k = cs->k;
+      cs->ibuilds.push_back(ib); cs->ibuildSlots.push_back(slot);
+    }
     T4CopyDesc d1; d1.srcOff = stOff + stagedBlob; d1.dst = (unsigned char *)(cs->dViews + slot); d1.bytes = viewBytes;
     cs->descs.push_back(d0); cs->descs.push_back(d1);
     cs->stUsed += stagedBlob + viewBytes;
   }
   memset(b, 0, stagedBlob + viewBytes);
   T4HashEntC *ht = (T4HashEntC *)b;   // full: the table; compact: the key records, in the order of the keys
-  if (!compact) for (size_t t = 0; t < sz; ++t) ht[t].code = ~0ull;   // empty slots
-  unsigned char *tail = b + headBytes;   // the image from oPost on
+  if (!compact && !indexed) for (size_t t = 0; t < sz; ++t) ht[t].code = ~0ull;   // empty slots
+  unsigned char *tail = b + headBytes - (tailFrom - oPost);   // where the image's byte oPost is, or would be, staged
   int2 *post = (int2 *)tail;
   const unsigned long long hashMask = sz - 1;
   size_t at = 0, kAt = 0;
-  for (size_t i = 0; i < nkeys; ++i) {
+  if (indexed) {   // the count bytes in the order of the consensus block: offset o of contig i at consOff(i) + o
+    size_t consAt = 0;
+    for (int i = 0; i < nseq; ++i) {
+      const size_t l = strlen(cons[i]);
+      size_t n = (postCnt && postCnt[i]) ? (postCntLen ? (size_t)(postCntLen[i] > 0 ? postCntLen[i] : 0) : l) : 0;
+      if (n > l) n = l;   // (zeros beyond the contig: checked above)
+      if (n) memcpy(b + consAt, postCnt[i], n);
+      consAt += l + 1;
+    }
+  }
+  for (size_t i = 0; i < (indexed ? 0 : nkeys); ++i) {
     const unsigned long long cd = keyCode[i];
     const int hb = keyBucket[i], cnt = keyCnt[i];
     for (int j = 0; j < cnt; ++j) {
@@ -2989,6 +3058,16 @@ int t4_cellstore_stage_compact(t4_cellstore *cs, int slot, int barcode, int nseq
                                const int32_t *const *pw, int64_t nkeys, const uint64_t *keyCode, const int32_t *keyBucket, const int32_t *keyCnt,
                                const int32_t *postIn, int64_t *pwOffsetInImage, const int32_t *seqBarcodes) {
   return cellStage(cs, true, slot, barcode, nseq, names, cons, pw, nkeys, keyCode, keyBucket, keyCnt, postIn, pwOffsetInImage, seqBarcodes);
+}
+int t4_cellstore_stage_indexed(t4_cellstore *cs, int slot, int barcode, int nseq, const char *const *names, const char *const *cons,
+                               const int32_t *const *pw, int64_t nkeys, int64_t npost, const uint8_t *const *postCnt, const int32_t *postCntLen,
+                               int64_t *pwOffsetInImage) {
+  return cellStage(cs, false, slot, barcode, nseq, names, cons, pw, nkeys, nullptr, nullptr, nullptr, nullptr, pwOffsetInImage, nullptr, true, npost, postCnt, postCntLen);
+}
+int t4_cellstore_indexed_stats(const t4_cellstore *cs, int64_t *out4) {
+  if (!cs || !out4) return T4_ERR_ARG;
+  out4[0] = cs->imagesIndexed; out4[1] = cs->countBytesShipped; out4[2] = cs->postingsIndexed; out4[3] = cs->tableBytesIndexed;
+  return T4_OK;
 }
 
 // Test and diagnostic aid: flush, then the image of the slot as it lies in the arena (its table, postings, sequence records,

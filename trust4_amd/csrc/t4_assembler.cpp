@@ -836,18 +836,29 @@ struct t4_assembler : IndexListener {
     else if (v > 0) --v;
     markBaseDirty(idx, off);
   }
+  // a cell's counts (the indexed image form ships them, stageImage; kept only for a cell set in that form): the same bytes, no dirty
+  // marks; a count that would pass 255 cannot be shipped as a byte, and the cell stages compact images from then on
+  bool keepCounts = false, countsOverflowed = false;
+  void cellCount(int idx, int off, int delta) {
+    if (!keepCounts || idx < 0 || idx >= (int)seqs.size() || off < 0) return;
+    Seq &q = seqs[idx];
+    if ((int)q.postCnt.size() <= off) q.postCnt.resize((size_t)off + 64, 0);
+    uint8_t &v = q.postCnt[(size_t)off];
+    if (delta > 0) { if (v == 255) countsOverflowed = true; else ++v; }
+    else if (v > 0) --v;
+  }
   void onInsert(uint64_t code, int h, int idx, int off, uint32_t sizeAfter) override {
-    if (!live()) { invalidateCell(); return; }
+    if (!live()) { cellCount(idx, off, +1); invalidateCell(); return; }
     postMark(idx, off, +1);
     if (!order.empty()) idxEvents.push_back(IdxEv{code, h, idx, off, +1, sizeAfter});
   }
   void onRemove(uint64_t code, int h, int idx, int off, uint32_t sizeAfter) override {
-    if (!live()) { invalidateCell(); return; }
+    if (!live()) { cellCount(idx, off, -1); invalidateCell(); return; }
     postMark(idx, off, -1);
     if (!order.empty()) idxEvents.push_back(IdxEv{code, h, idx, off, -1, sizeAfter});
   }
   void onMove(uint64_t code, int h, int oldIdx, int oldOff, int idx, int off) override {
-    if (!live()) { invalidateCell(); return; }
+    if (!live()) { cellCount(oldIdx, oldOff, -1); cellCount(idx, off, +1); invalidateCell(); return; }
     postMark(oldIdx, oldOff, -1); postMark(idx, off, +1);
     if (order.empty() || oldIdx == idx) return;   // a shift of one contig's postings is one structural event (evShift)
     idxEvents.push_back(IdxEv{code, h, oldIdx, oldOff, -1, 0xFFFFFFFFu});   // sizes unchanged
@@ -950,6 +961,13 @@ struct t4_assembler : IndexListener {
   int64_t verified = 0, verifiedMerged = 0;
   void beginWindow(int n, const char *const *reads, const int *strands, const int *barcodes, int repetitive);
   void endWindow(const int32_t *cnts, const t4_overlap *ov, const t4_overlap *ex, const int32_t *rets, int stride);
+  bool fallbackCounted = false;
+  void recount() {   // the counts from the index as it stands (the form was chosen after the cell got its first contigs)
+    for (Seq &q : seqs) q.postCnt.clear();
+    for (const auto &kv : index.map)
+      for (uint32_t t = 0; t < kv.second.cnt; ++t) cellCount(index.arena[kv.second.start + t].idx, index.arena[kv.second.start + t].offset, +1);
+  }
+  bool indexedImage();   // cell mode: this cell's next image goes in the indexed form (the owner asked for it, no count outgrew its byte)
   int stageImage();   // cell mode: queue this cell's image in the owner's arena
   int releaseFinishedBarcode(int barcode, int contigMinCov);
   bool isContigShallow(int i, int minCov) const;
@@ -1071,7 +1089,7 @@ struct t4_assembler : IndexListener {
     std::vector<Seq> kept;
     for (Seq &s : seqs) if (!s.released) kept.push_back(std::move(s));
     seqs.swap(kept);
-    for (Seq &s : seqs) { s.postCnt.clear(); s.marksBad = false; }   // (the builds below mark every posting of the new index)
+    for (Seq &s : seqs) { s.postCnt.clear(); s.marksBad = false; }   // (the builds below mark, or count, every posting of the new index)
     for (int i = 0; i < (int)seqs.size(); ++i) index.build(seqs[i].cons.c_str(), (int)seqs[i].cons.size(), i, seqs[i].barcode, 0);
     setPrev(-1, -1, -1, -1, -1, 0);
     if (dev) { t4_index_destroy(dev); dev = nullptr; }   // nomatchGapLimit and the lookup layout depend on k
@@ -1470,6 +1488,9 @@ struct t4_cellset {
   int64_t queries = 0, readsQueried = 0, batchSeq = 0;
   std::atomic<int64_t> stagedImages{0}, stagedLiveKeys{0};   // images handed to the store; keys with postings over those images, counted here
   double secQuery = 0, secStage = 0;
+  int imageForm = T4_CELL_IMAGE_COMPACT;   // t4_cellset_set_image_form
+  std::atomic<int64_t> fallbackCells{0}, imagesCrosschecked{0};   // cells whose counts outgrew a byte; indexed images held against index.map (test builds)
+  bool crosscheck = false, prefetched = false;
   int threads = 1;   // host threads for image builds and window bookkeeping (cells are independent)
   std::unique_ptr<t4_overlap[]> resOv, resEx;
   std::unique_ptr<int32_t[]> resRet;
@@ -1477,6 +1498,11 @@ struct t4_cellset {
   std::string err;
 };
 
+bool t4_assembler::indexedImage() {
+  if (!owner || owner->imageForm != T4_CELL_IMAGE_INDEXED) return false;
+  if (countsOverflowed && !fallbackCounted) { fallbackCounted = true; ++owner->fallbackCells; }
+  return !countsOverflowed;
+}
 int t4_assembler::stageImage() {   // thread-safe across cells once the owner has run t4_cellstore_prepare
   if (!dirty) return T4_OK;
   int r;
@@ -1490,6 +1516,45 @@ int t4_assembler::stageImage() {   // thread-safe across cells once the owner ha
     names[i] = gone ? "" : q.name.c_str();
     cons[i] = gone ? "" : q.cons.c_str();
     pw[i] = (gone || q.pw.empty()) ? nullptr : (const int32_t *)q.pw.data();
+  }
+  if (indexedImage()) {   // the index travels as the contigs' counts: the map is not walked
+    std::vector<const uint8_t *> cnt(n);
+    std::vector<int32_t> cntLen(n);
+    for (int i = 0; i < n; ++i) {
+      const Seq &q = seqs[i];
+      cnt[i] = (q.released || q.postCnt.empty()) ? nullptr : q.postCnt.data();
+      cntLen[i] = cnt[i] ? (int32_t)std::min(q.postCnt.size(), q.cons.size()) : 0;
+    }
+#ifdef T4_TEST_KNOBS
+    if (owner->crosscheck) {   // T4_TEST_IMAGE_CROSSCHECK: the maintained counts against the ones the map gives
+      std::vector<std::vector<int>> want(n);
+      for (int i = 0; i < n; ++i) want[i].assign(seqs[i].released ? 0 : seqs[i].cons.size() + 1, 0);
+      bool ok = true;
+      for (const auto &kv : index.map)
+        for (uint32_t t = 0; t < kv.second.cnt; ++t) {
+          const Post &p = index.arena[kv.second.start + t];
+          if (p.idx < 0 || p.idx >= n || p.offset < 0 || (size_t)p.offset >= want[p.idx].size()) { ok = false; continue; }
+          ++want[p.idx][(size_t)p.offset];
+        }
+      for (int i = 0; i < n && ok; ++i) {
+        for (size_t o = 0; o < want[i].size() && ok; ++o) ok = want[i][o] == ((int)o < cntLen[i] ? (int)cnt[i][o] : 0);
+        // (counts kept beyond what is shipped must be zeros)
+        if (!seqs[i].released) for (size_t o = (size_t)cntLen[i]; o < seqs[i].postCnt.size() && ok; ++o) ok = seqs[i].postCnt[o] == 0;
+      }
+      if (!ok) { fprintf(stderr, "t4_assembler: the posting counts of cell %d differ from its index\n", cellBarcode); return T4_ERR_STATE; }
+      ++owner->imagesCrosschecked;
+    }
+#endif
+    int64_t oPw = 0;
+    r = t4_cellstore_stage_indexed(owner->store, slot, cellBarcode, n, names.data(), cons.data(), pw.data(), (int64_t)index.map.size(), (int64_t)index.total,
+                                   cnt.data(), cntLen.data(), &oPw);
+    if (r) return r;
+    imgPwOff.resize(n);
+    for (int i = 0; i < n; ++i) { imgPwOff[i] = oPw; oPw += (int64_t)strlen(cons[i]) + 1; }
+    patches.clear();
+    dirty = false; ++refreshes;
+    ++owner->stagedImages;
+    return T4_OK;
   }
   // one list per (code, bucket) key, postings in the replica's order; the order of the keys does not matter to a hash table
   static thread_local std::vector<uint64_t> keyCode; static thread_local std::vector<int32_t> keyBucket, keyCnt, post;
@@ -3271,6 +3336,9 @@ int t4_cellset_create(t4_ctx *ctx, int kmer_length, t4_cellset **out) {
   cs->ctx = ctx; cs->k = kmer_length;
   int r = t4_cellstore_create(ctx, kmer_length, &cs->store);
   if (r) { delete cs; return r; }
+#ifdef T4_TEST_KNOBS
+  cs->crosscheck = getenv("T4_TEST_IMAGE_CROSSCHECK") != nullptr && atoi(getenv("T4_TEST_IMAGE_CROSSCHECK")) != 0;
+#endif
   *out = cs;
   return T4_OK;
 }
@@ -3292,7 +3360,7 @@ int t4_cellset_cell(t4_cellset *cs, int barcode, t4_assembler **cell) {
   if (it == cs->cells.end()) {
     t4_assembler *a = new t4_assembler(cs->ctx, cs->k);
     a->index.considerBarcode = true;
-    a->owner = cs; a->cellBarcode = barcode;
+    a->owner = cs; a->cellBarcode = barcode; a->keepCounts = cs->imageForm == T4_CELL_IMAGE_INDEXED;
     a->hitLenRequired = cs->hitLenRequired; a->radius = cs->radius; a->novelSim = cs->novelSim;
     it = cs->cells.emplace(barcode, a).first;
   }
@@ -3312,6 +3380,7 @@ int t4_cellset_prefetch(t4_cellset *cs, int n, t4_assembler *const *cells, const
   if (!cs || n < 0 || (n > 0 && (!cells || !reads || !strands))) return T4_ERR_ARG;
   const int MAXOV = 128;
   const int rep = repetitive_data ? 1 : 0;
+  cs->prefetched = true;
   ++cs->batchSeq;
   // the reads of one cell must be consecutive (its speculation window, in the order they will be offered)
   int rc;
@@ -3346,7 +3415,8 @@ int t4_cellset_prefetch(t4_cellset *cs, int n, t4_assembler *const *cells, const
     if (cell->dirty) {
       int64_t consBytes = 0;
       for (const Seq &q : cell->seqs) consBytes += (q.released ? 0 : (int64_t)q.cons.size()) + 1;
-      stageBytes += t4_cellstore_image_bytes((int)cell->seqs.size(), (int64_t)cell->index.map.size(), (int64_t)cell->index.total, consBytes);
+      stageBytes += cell->indexedImage() ? t4_cellstore_indexed_image_bytes((int)cell->seqs.size(), consBytes)
+                                         : t4_cellstore_image_bytes((int)cell->seqs.size(), (int64_t)cell->index.map.size(), (int64_t)cell->index.total, consBytes);
     }
   }
   if ((rc = t4_cellstore_prepare(cs->store, maxSlot, stageBytes))) return rc;
@@ -3445,6 +3515,26 @@ int t4_cellset_counters(const t4_cellset *cs, int64_t *query_batches, int64_t *r
   if (bytes_staged) *bytes_staged = t4_cellstore_bytes_staged(cs->store);
   if (sec_query) *sec_query = cs->secQuery;
   if (sec_stage) *sec_stage = cs->secStage;
+  return T4_OK;
+}
+int t4_cellset_set_image_form(t4_cellset *cs, int form) {
+  if (!cs || (form != T4_CELL_IMAGE_COMPACT && form != T4_CELL_IMAGE_INDEXED)) return T4_ERR_ARG;
+  if (cs->prefetched) return T4_ERR_STATE;
+  cs->imageForm = form;
+  for (auto &kv : cs->cells) {
+    const bool was = kv.second->keepCounts;
+    kv.second->keepCounts = form == T4_CELL_IMAGE_INDEXED;
+    if (kv.second->keepCounts && !was) kv.second->recount();
+  }
+  return T4_OK;
+}
+int t4_cellset_indexed_stats(const t4_cellset *cs, int64_t *out, int n) {
+  if (!cs || !out || n < 0) return T4_ERR_ARG;
+  int64_t v[6];
+  int r = t4_cellstore_indexed_stats(cs->store, v);
+  if (r) return r;
+  v[4] = cs->fallbackCells.load(); v[5] = cs->imagesCrosschecked.load();
+  for (int i = 0; i < n && i < 6; ++i) out[i] = v[i];
   return T4_OK;
 }
 int64_t t4_cellset_live_keys_staged(const t4_cellset *cs) { return cs ? cs->stagedLiveKeys.load() : 0; }

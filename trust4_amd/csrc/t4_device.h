@@ -307,3 +307,7 @@ static_assert(offsetof(T4AqTail, poolCursor) == 24 && offsetof(T4AqTail, candCur
 struct T4BytePatch { unsigned char *dst; unsigned long long val; };   // one posWeight predicate byte of a resident image
 struct T4CopyDesc { unsigned long long srcOff; unsigned char *dst; unsigned long long bytes; };  // scatter of staged set images
 struct T4TableBuild { T4HashEntC *table; unsigned long long tableSlots, srcOff, nKeys; };   // table of a set image built on the device from nKeys staged (code, start, cnt) records
+// table AND postings of a set image built on the device from its contigs (cellIndexBuildKernel): the staged count bytes (one per
+// consensus byte, cntOff), sequence records (seqOff) and consensus block (consOff) of the image, all offsets into the staging buffer
+struct T4IndexBuild { T4HashEntC *table; int2 *post; unsigned long long tableSlots, cntOff, seqOff, consOff; unsigned consBytes, npost; int nseq, k; };
+enum { T4_IDXERR_KMER = 1 /* a counted offset without a whole ACGT k-mer */, T4_IDXERR_FULL = 2 /* no free table slot */, T4_IDXERR_TOTAL = 3 /* the counts do not add up to npost */ };

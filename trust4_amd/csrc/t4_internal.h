@@ -31,6 +31,23 @@ int t4_cellstore_stage(t4_cellstore *cs, int slot, int barcode, int nseq, const 
 int t4_cellstore_stage_compact(t4_cellstore *cs, int slot, int barcode, int nseq, const char *const *names, const char *const *cons,
                                const int32_t *const *pw, int64_t nkeys, const uint64_t *key_code, const int32_t *key_bucket,
                                const int32_t *key_cnt, const int32_t *post, int64_t *pw_offset_in_image, const int32_t *seq_barcodes);
+// The same image with its table AND its postings built on the device from the image's own contigs (the indexed form): every posting
+// (i, o) of a cell's index has the code of contig i's k-mer at o, so the index travels as one count byte per consensus byte --
+// post_cnt[i][o] = the postings (i, o) the index holds; post_cnt_len[i] bytes of contig i are given (post_cnt_len null: as many as
+// the contig has bases), a null post_cnt[i] and every byte not given mean zero. Staging receives [count bytes, padded to 16]
+// [image from its sequence records on] [view]; the flush runs cellIndexBuildKernel ahead of the scatter. The table has the slots
+// of nkeys keys (the image's layout is that of t4_cellstore_stage with nkeys keys and npost postings; everything from the sequence
+// records on and the view are byte-equal), so nkeys must be at least the distinct k-mers counted. Every contig carries `barcode`.
+// Refused here with T4_ERR_ARG, nothing queued: a count at an offset o with o + k beyond the contig, counts that do not add up to
+// npost, npost > 0 with nkeys == 0. Refused by the flush (T4_ERR_ARG naming the slot, which is to be staged again; the other images of
+// the flush are whole): a counted offset whose k-mer holds a letter outside ACGT, more distinct k-mers than the table can hold.
+int t4_cellstore_stage_indexed(t4_cellstore *cs, int slot, int barcode, int nseq, const char *const *names, const char *const *cons,
+                               const int32_t *const *pw, int64_t nkeys, int64_t npost, const uint8_t *const *post_cnt,
+                               const int32_t *post_cnt_len, int64_t *pw_offset_in_image);
+size_t t4_cellstore_indexed_image_bytes(int nseq, int64_t cons_bytes);   // staged size of one such image, exact
+// 4 values: images indexed on the device, count bytes shipped for them (padded), postings written on the device, table bytes
+// written on the device (16 per slot). t4_cellstore_image_stats' first three values do not count these images; its fourth does.
+int t4_cellstore_indexed_stats(const t4_cellstore *cs, int64_t *out4);
 // Overwrite posWeight predicate bytes of the slot's resident image (byte offsets as returned by the last stage + the
 // column's index); applied after the staged images of the same flush.
 int t4_cellstore_patch(t4_cellstore *cs, int slot, int n, const int64_t *byte_offsets, const unsigned char *values);

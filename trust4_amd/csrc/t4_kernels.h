@@ -4416,6 +4416,122 @@ __global__ __launch_bounds__(256) void cellTableBuildKernel(const unsigned char 
   }
 }
 
+// Byte i of an image's count block counts the postings (s, o): s is the contig whose consensus holds byte i (the last one with
+// consOff <= i; every contig owns at least its terminator, so the offsets rise strictly), o = i - consOff(s). Their key is the code of
+// cons[s][o .. o + K) as expandHitsContig forms it -- 2 bits per base, first base most significant, masked to 2 K bits -- which is
+// the code the host's map files them under. false: the offset has no whole k-mer of ACGT.
+__device__ __forceinline__ bool cellIndexKey(const T4SeqInfo *seqs, const char *cons, int nseq, int K, unsigned i, int &s, int &o, unsigned long long &code) {
+  if (nseq <= 0) return false;
+  int lo = 0, hi = nseq - 1;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if ((unsigned)seqs[mid].consOff <= i) lo = mid; else hi = mid - 1; }
+  const int consOff = seqs[lo].consOff, len = seqs[lo].len;
+  s = lo; o = (int)i - consOff;
+  if (o < 0 || o + K > len) return false;
+  bool ok = true;
+  code = 0;
+  for (int t = 0; t < K; ++t) { const char ch = cons[consOff + o + t]; if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') ok = false; code = (code << 2) | (unsigned long long)nuc2(ch); }
+  code &= K < 32 ? ((1ull << (2 * K)) - 1ull) : ~0ull;
+  return ok;
+}
+
+// Table AND postings of freshly staged per-barcode set images, built where they live from the image's own contigs: every posting
+// (s, o) of a cell's index has the code of the contig's k-mer at o, so one count byte per consensus byte -- how many postings (s, o)
+// the index holds -- says all the index says, and the order inside a posting list is not observable (the hits are sorted). One
+// workgroup per image; everything is read from STAGING (the scatter of the same flush writes the slot after this kernel), the table
+// and the postings are written in the slot. Four phases, a fence and a barrier between them:
+//   clear  every table slot empty, (~0, 0, 0)
+//   count  per counted offset: probe from mix64(code) & mask, claim an empty slot by a compare-and-swap of its code or meet the same
+//          code (the same key: the normal case here), add the count byte to the slot's cnt
+//   scan   exclusive prefix sum of cnt over the slots, in slot order, gives every start; every cnt back to 0; the total is npost
+//   fill   the same offsets again: p = start + (cnt += m) of the key's slot, m copies of (s, o) at post[p ..); cnt ends where the
+//          count phase left it
+// Which thread claims a slot or a position decides where a key or a posting lands, never the map, a list's multiset of postings or
+// that the lists tile [0, npost). A counted offset without a whole ACGT k-mer, a probe all the way round or a total other than npost
+// ends the work on that image: the first such image of a launch leaves {its number + 1, T4_IDXERR_*} in err[0..1].
+__global__ __launch_bounds__(256) void cellIndexBuildKernel(const unsigned char *staging, const T4IndexBuild *build, int nBuild, int *err) {
+  __shared__ unsigned s_scan[256];
+  __shared__ int s_err;
+  for (int b = blockIdx.x; b < nBuild; b += gridDim.x) {
+    const T4IndexBuild ib = build[b];
+    if (threadIdx.x == 0) s_err = 0;
+    uint4 empty; empty.x = ~0u; empty.y = ~0u; empty.z = 0u; empty.w = 0u;
+    uint4 *slots = (uint4 *)ib.table;
+    for (unsigned long long i = threadIdx.x; i < ib.tableSlots; i += blockDim.x) slots[i] = empty;
+    __threadfence();
+    __syncthreads();
+    const unsigned *cntWords = (const unsigned *)(staging + ib.cntOff);   // (the count block is padded to 16 bytes with zeros)
+    const T4SeqInfo *seqs = (const T4SeqInfo *)(staging + ib.seqOff);
+    const char *cons = (const char *)(staging + ib.consOff);
+    const unsigned nWords = (ib.consBytes + 3u) >> 2;
+    const unsigned long long mask = ib.tableSlots - 1;
+    for (unsigned w = threadIdx.x; w < nWords; w += blockDim.x) {
+      const unsigned word = cntWords[w];
+      for (unsigned q = 0; q < 4u && word; ++q) {
+        const unsigned m = (word >> (8u * q)) & 255u;
+        if (!m) continue;
+        int s, o;
+        unsigned long long code;
+        if (!cellIndexKey(seqs, cons, ib.nseq, ib.k, 4u * w + q, s, o, code)) { s_err = T4_IDXERR_KMER; break; }
+        unsigned long long at = mix64(code) & mask, probes = 0;
+        for (; probes < ib.tableSlots; ++probes) {
+          const unsigned long long seen = atomicCAS(&ib.table[at].code, ~0ull, code);
+          if (seen == ~0ull || seen == code) break;
+          at = (at + 1) & mask;
+        }
+        if (probes == ib.tableSlots) { s_err = T4_IDXERR_FULL; break; }
+        atomicAdd(&ib.table[at].cnt, m);
+      }
+    }
+    __threadfence();
+    __syncthreads();
+    int e = s_err;
+    __syncthreads();
+    if (!e) {
+      // (tableSlots is a power of two from 64: a run of tableSlots / 256 slots per thread, or one slot for the first threads)
+      const unsigned long long per = ib.tableSlots >= 256ull ? ib.tableSlots >> 8 : 1ull, first = threadIdx.x * per;
+      unsigned sum = 0;
+      if (first < ib.tableSlots)
+        for (unsigned long long j = first; j < first + per; ++j) { const unsigned v = atomicExch(&ib.table[j].cnt, 0u); ib.table[j].start = v; sum += v; }
+      s_scan[threadIdx.x] = sum;
+      __syncthreads();
+      for (unsigned d = 1; d < 256u; d <<= 1) {
+        const unsigned add = threadIdx.x >= d ? s_scan[threadIdx.x - d] : 0u;
+        __syncthreads();
+        s_scan[threadIdx.x] += add;
+        __syncthreads();
+      }
+      if (threadIdx.x == 255 && s_scan[255] != ib.npost) s_err = T4_IDXERR_TOTAL;
+      unsigned run = s_scan[threadIdx.x] - sum;
+      if (first < ib.tableSlots)
+        for (unsigned long long j = first; j < first + per; ++j) { const unsigned v = ib.table[j].start; ib.table[j].start = v ? run : 0u; run += v; }   // (an empty slot stays (~0, 0, 0))
+      __threadfence();
+      __syncthreads();
+      e = s_err;
+      __syncthreads();
+    }
+    if (e) {   // the image stays as far as it got: its slot is staged again before anything reads it
+      if (threadIdx.x == 0 && atomicCAS(&err[0], 0, b + 1) == 0) err[1] = e;
+      continue;
+    }
+    for (unsigned w = threadIdx.x; w < nWords; w += blockDim.x) {
+      const unsigned word = cntWords[w];
+      for (unsigned q = 0; q < 4u && word; ++q) {
+        const unsigned m = (word >> (8u * q)) & 255u;
+        if (!m) continue;
+        int s, o;
+        unsigned long long code;
+        if (!cellIndexKey(seqs, cons, ib.nseq, ib.k, 4u * w + q, s, o, code)) continue;   // (the count phase has seen every one)
+        unsigned long long at = mix64(code) & mask, probes = 0;
+        while (probes < ib.tableSlots && ib.table[at].code != code) { at = (at + 1) & mask; ++probes; }
+        if (probes == ib.tableSlots) continue;
+        const unsigned p = ib.table[at].start + atomicAdd(&ib.table[at].cnt, m);
+        if ((unsigned long long)p + m > ib.npost) continue;   // (cannot happen once the total was npost: no store leaves the postings)
+        for (unsigned t = 0; t < m; ++t) ib.post[p + t] = make_int2(s, o);
+      }
+    }
+  }
+}
+
 // Patches of a live set's image (t4_index_apply_delta): run d copies bytes staging[srcOff ..) -> dst, one wavefront per run.
 // Runs never overlap (every destination is written once per delta).
 __global__ __launch_bounds__(256) void deltaKernel(const unsigned char *staging, const T4CopyDesc *desc, int nDesc) {
