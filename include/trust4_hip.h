@@ -388,8 +388,19 @@ int t4_cellset_image_stats(const t4_cellset *cs, int64_t *out, int n);
  * cell's arena slot from them. The device image differs from the compact form's only in where keys and postings lie; queries
  * answer the same. A cell in which one offset collects more than 255 postings goes back to the compact form for good.
  * To be called before the first t4_cellset_prefetch (T4_ERR_STATE afterwards); T4_ERR_ARG for any other form. */
-enum { T4_CELL_IMAGE_COMPACT = 0, T4_CELL_IMAGE_INDEXED = 1 };
+/* T4_CELL_IMAGE_RESIDENT goes one step further: the image stays in the cell's arena slot between rounds, every contig in a stretch of
+ * its own with room to grow, next to its count bytes. The first image of a cell travels whole; after that a change travels as the
+ * contigs it touched (consensus, predicate bytes, counts, name; a new contig and a released one are touched contigs), the device
+ * copies them into their stretches and rebuilds table and postings from what the slot then holds. A contig that outgrows its
+ * stretch, more contigs than the slot has records for, or more postings than its table serves send the cell through a whole image
+ * again, with a fresh layout. Queries answer the same as in the other forms. The cell keeps its host index in this form too. */
+enum { T4_CELL_IMAGE_COMPACT = 0, T4_CELL_IMAGE_INDEXED = 1, T4_CELL_IMAGE_RESIDENT = 2 };
 int t4_cellset_set_image_form(t4_cellset *cs, int form);
+/* The resident form's counters, the first min(n, 8) of: images staged whole; deltas; contigs shipped by deltas; deltas the store sent
+ * back for a whole image (0 for a cell set, which asks before it stages); whole images of slots that held a resident image already
+ * (a delta did not fit, or nothing but the view changed); postings written on the device; table bytes written on the device (16 per
+ * slot); cells that went back to the compact form (a count past 255). */
+int t4_cellset_resident_stats(const t4_cellset *cs, int64_t *out, int n);
 /* The indexed form's own counters, the first min(n, 6) of: images whose table and postings were built on the device; count bytes
  * shipped for them; postings written on the device; table bytes written on the device (16 per slot); cells that went back to the
  * compact form (a count past 255); images whose counts were checked against the host's index (test builds only, else 0).

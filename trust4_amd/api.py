@@ -94,7 +94,7 @@ def _load():
         "t4_cellset_close_cell": (I, [P, P]), "t4_cellset_prefetch": (I, [P, I, P, P, P, I]),
         "t4_cellset_update_all_consensus": (I, [P]), "t4_cellset_set_threads": (I, [P, I]), "t4_cellset_size": (I, [P]),
         "t4_cellset_output": (I, [P, C.c_char_p, P, I]), "t4_cellset_counters": (I, [P, P, P, P, P, P, P]),
-        "t4_cellset_image_stats": (I, [P, P, I]), "t4_cellset_set_image_form": (I, [P, I]), "t4_cellset_indexed_stats": (I, [P, P, I]),
+        "t4_cellset_image_stats": (I, [P, P, I]), "t4_cellset_set_image_form": (I, [P, I]), "t4_cellset_indexed_stats": (I, [P, P, I]), "t4_cellset_resident_stats": (I, [P, P, I]),
         # library-internal calls of the AddRead query (csrc/t4_internal.h): what a restricted re-query is driven with
         "t4_add_query_pool_begin2": (I, [P, I, P, P, P, P, I, P, P, P, P, I]), "t4_add_query_pool_end": (I, [P] + [C.POINTER(P)] * 5),
         "t4_add_query_last_cands": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(I)]),
@@ -483,11 +483,12 @@ class CellSet:
         self.eng.check(self.eng.lib.t4_cellset_image_stats(self.h, C.cast(v, C.c_void_p), 4))
         return {"images_built_on_device": v[0], "key_records_shipped": v[1], "table_bytes_built_on_device": v[2], "bytes_staged": v[3]}
 
-    IMAGE_FORMS = {"compact": 0, "indexed": 1}   # T4_CELL_IMAGE_COMPACT / T4_CELL_IMAGE_INDEXED
+    IMAGE_FORMS = {"compact": 0, "indexed": 1, "resident": 2}   # T4_CELL_IMAGE_COMPACT / T4_CELL_IMAGE_INDEXED / T4_CELL_IMAGE_RESIDENT
 
     def set_image_form(self, form):
         """the form the cells' images travel in, before the first prefetch: "compact" (default) or "indexed" (no index shipped:
-        the device builds table and postings from the contigs and one count byte per consensus position)"""
+        the device builds table and postings from the contigs and one count byte per consensus position) or "resident" (the image
+        stays in its slot, a change travels as the contigs it touched, the device rebuilds table and postings from the slot)"""
         self.eng.check(self.eng.lib.t4_cellset_set_image_form(self.h, self.IMAGE_FORMS.get(form, form)))
 
     def indexed_stats(self):
@@ -495,6 +496,12 @@ class CellSet:
         self.eng.check(self.eng.lib.t4_cellset_indexed_stats(self.h, C.cast(v, C.c_void_p), 6))
         return {"images_indexed_on_device": v[0], "count_bytes_shipped": v[1], "postings_built_on_device": v[2],
                 "table_bytes_indexed_on_device": v[3], "cells_fallen_back_to_compact": v[4], "images_crosschecked": v[5]}
+
+    def resident_stats(self):
+        v = (C.c_int64 * 8)()
+        self.eng.check(self.eng.lib.t4_cellset_resident_stats(self.h, C.cast(v, C.c_void_p), 8))
+        return {"images_resident_whole": v[0], "deltas": v[1], "delta_contigs_shipped": v[2], "deltas_sent_back": v[3], "whole_restages": v[4],
+                "postings_rebuilt_on_device": v[5], "table_bytes_rebuilt_on_device": v[6], "cells_fallen_back_to_compact": v[7]}
 
     def close(self):
         if getattr(self, "h", None):

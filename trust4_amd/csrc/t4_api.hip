@@ -2641,7 +2641,17 @@ struct t4_cellstore {
   t4_ctx *ctx = nullptr;
   int k = 9, hitLenRequired = 31, radius = 10, nomatchGapLimit = 0;
   double novelSim = 0.9;
-  struct Slot { unsigned char *base = nullptr; size_t cap = 0, imgBytes = 0; bool live = false; bool pending = false; };
+  // The resident form's layout of a slot (t4_cellstore_stage_delta; T4DeltaRec in t4_device.h): [table: tableSlots] [postings: as
+  // many as a table of tableSlots may serve] [records: seqCap] [predicate bytes | consensus | count bytes: stretchCap bytes each], contig
+  // i in [off[i], off[i] + cap[i]) of each of the three blocks; stretches are handed out in the order of the contigs and never move.
+  struct Resident {
+    bool on = false;
+    size_t tableSlots = 0, postCap = 0, oPost = 0, oSeq = 0, oPw = 0, oCons = 0, oCnt = 0, stretchCap = 0, stretchUsed = 0;
+    int seqCap = 0, nseq = 0;
+    std::vector<uint32_t> off, cap, len;
+    std::vector<int64_t> cntSum;   // postings counted on every contig: the total of a delta is checked without the untouched contigs' bytes
+  };
+  struct Slot { unsigned char *base = nullptr; size_t cap = 0, imgBytes = 0; bool live = false; bool pending = false; Resident res; };
   std::vector<Slot> slots;
   std::vector<int> freeIds;
   std::vector<DevBuf<unsigned char>> chunks;   // (Slot::base and freeBySize point into these)
@@ -2665,6 +2675,13 @@ struct t4_cellstore {
   DevBuf<int> dBuildErr; PinnedBuf<int> hBuildErr;
   int64_t imagesBuilt = 0, keysShipped = 0, tableBytesBuilt = 0;
   int64_t imagesIndexed = 0, countBytesShipped = 0, postingsIndexed = 0, tableBytesIndexed = 0;
+  std::vector<T4DeltaApply> deltas;   // resident images of this flush, whole ones and deltas (t4_cellstore_stage_delta)
+  // resident form: images staged whole, deltas, contigs shipped by deltas, deltas that did not fit their slot (the caller staged
+  // the cell whole), whole images of slots that held a resident image already, postings and table bytes written on the device
+  int64_t residentWhole = 0, residentDeltas = 0, deltaContigs = 0, deltaMisfits = 0, residentRestages = 0, postingsResident = 0, tableBytesResident = 0;
+#ifdef T4_TEST_KNOBS
+  bool dropFirstTouched = false;   // T4_TEST_DELTA_DROP: a delta loses its first touched contig on the way (the tests' negative control)
+#endif
   std::vector<T4BytePatch> patches;
   DevBuf<T4BytePatch> dPatches;
   size_t patchCap = 0;
@@ -2723,10 +2740,12 @@ int cellFlushPatches(t4_cellstore *cs) {
   return T4_OK;
 }
 int cellFlush(t4_cellstore *cs) {
-  if (cs->descs.empty()) return cellFlushPatches(cs);
+  if (cs->descs.empty() && cs->deltas.empty()) return cellFlushPatches(cs);
   t4_ctx *c = cs->ctx;
+  // control block: [copy descriptors] [table builds] [index builds] [resident deltas], every part a multiple of 8 bytes
   const size_t descBytes = (sizeof(T4CopyDesc) * cs->descs.size() + 15) & ~(size_t)15, tblBytes = sizeof(T4TableBuild) * cs->builds.size(),
-               buildBytes = tblBytes + sizeof(T4IndexBuild) * cs->ibuilds.size();
+               idxBytes = sizeof(T4IndexBuild) * cs->ibuilds.size(), deltaBytes = sizeof(T4DeltaApply) * cs->deltas.size(),
+               buildBytes = tblBytes + idxBytes + deltaBytes;
   if (descBytes + buildBytes > cs->descCap) {
     if (cs->dDescs) (void)hipStreamSynchronize(c->stream);
     cs->descCap = 0;
@@ -2738,7 +2757,8 @@ int cellFlush(t4_cellstore *cs) {
     cs->ctlHost.resize(descBytes + buildBytes);
     memcpy(cs->ctlHost.data(), cs->descs.data(), sizeof(T4CopyDesc) * cs->descs.size());
     if (tblBytes) memcpy(cs->ctlHost.data() + descBytes, cs->builds.data(), tblBytes);
-    if (buildBytes > tblBytes) memcpy(cs->ctlHost.data() + descBytes + tblBytes, cs->ibuilds.data(), buildBytes - tblBytes);
+    if (idxBytes) memcpy(cs->ctlHost.data() + descBytes + tblBytes, cs->ibuilds.data(), idxBytes);
+    if (deltaBytes) memcpy(cs->ctlHost.data() + descBytes + tblBytes + idxBytes, cs->deltas.data(), deltaBytes);
     ctl = cs->ctlHost.data();
   }
   HIPCHK(c, hipMemcpyAsync(cs->stDev, cs->stHost, cs->stUsed, hipMemcpyHostToDevice, c->stream));
@@ -2750,6 +2770,13 @@ int cellFlush(t4_cellstore *cs) {
       if ((r = cs->dBuildErr.alloc(c, 4))) return r;
       HIPCHK(c, hipMemsetAsync(cs->dBuildErr, 0, sizeof(int) * 4, c->stream));
     }
+    if (deltaBytes) {   // the touched contigs of the resident images into their stretches, ahead of the builds that read them there
+      int bgrid = (int)cs->deltas.size();
+      if (bgrid > c->cus * 8) bgrid = c->cus * 8;
+      hipLaunchKernelGGL(t4k::cellDeltaApplyKernel, dim3(bgrid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev.p,
+                         (const T4DeltaApply *)(cs->dDescs.p + descBytes + tblBytes + idxBytes), (int)cs->deltas.size());
+      HIPCHK(c, hipGetLastError());
+    }
     if (tblBytes) {
       int bgrid = (int)cs->builds.size();
       if (bgrid > c->cus * 8) bgrid = c->cus * 8;
@@ -2757,7 +2784,7 @@ int cellFlush(t4_cellstore *cs) {
                          (const T4TableBuild *)(cs->dDescs.p + descBytes), (int)cs->builds.size(), cs->dBuildErr.p);
       HIPCHK(c, hipGetLastError());
     }
-    if (buildBytes > tblBytes) {
+    if (idxBytes) {
       int bgrid = (int)cs->ibuilds.size();
       if (bgrid > c->cus * 8) bgrid = c->cus * 8;
       hipLaunchKernelGGL(t4k::cellIndexBuildKernel, dim3(bgrid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev.p,
@@ -2766,10 +2793,12 @@ int cellFlush(t4_cellstore *cs) {
     }
     HIPCHK(c, hipMemcpyAsync(cs->hBuildErr, cs->dBuildErr, sizeof(int) * 4, hipMemcpyDeviceToHost, c->stream));
   }
-  int grid = (int)cs->descs.size();
-  if (grid > c->cus * 8) grid = c->cus * 8;
-  hipLaunchKernelGGL(t4k::scatterKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev.p, (const T4CopyDesc *)cs->dDescs.p, (int)cs->descs.size());
-  HIPCHK(c, hipGetLastError());
+  if (!cs->descs.empty()) {
+    int grid = (int)cs->descs.size();
+    if (grid > c->cus * 8) grid = c->cus * 8;
+    hipLaunchKernelGGL(t4k::scatterKernel, dim3(grid), dim3(256), 0, c->stream, (const unsigned char *)cs->stDev.p, (const T4CopyDesc *)cs->dDescs.p, (int)cs->descs.size());
+    HIPCHK(c, hipGetLastError());
+  }
   // the pageable descriptor vector and the pinned staging are reused by the next stage() calls
   HIPCHK(c, hipStreamSynchronize(c->stream));
   cs->bytesStaged += (int64_t)cs->stUsed;
@@ -2777,8 +2806,9 @@ int cellFlush(t4_cellstore *cs) {
   if (buildBytes) {
     cs->imagesBuilt += (int64_t)cs->builds.size();
     for (const T4TableBuild &tb : cs->builds) { cs->keysShipped += (int64_t)tb.nKeys; cs->tableBytesBuilt += (int64_t)(sizeof(T4HashEntC) * tb.tableSlots); }
-    cs->imagesIndexed += (int64_t)cs->ibuilds.size();
     for (const T4IndexBuild &ib : cs->ibuilds) {
+      if (ib.src) { cs->postingsResident += (int64_t)ib.npost; cs->tableBytesResident += (int64_t)(sizeof(T4HashEntC) * ib.tableSlots); continue; }
+      ++cs->imagesIndexed;
       cs->countBytesShipped += (int64_t)((ib.consBytes + 15u) & ~15u); cs->postingsIndexed += (int64_t)ib.npost;
       cs->tableBytesIndexed += (int64_t)(sizeof(T4HashEntC) * ib.tableSlots);
     }
@@ -2790,7 +2820,9 @@ int cellFlush(t4_cellstore *cs) {
       (void)hipStreamSynchronize(c->stream);
     }
   }
-  cs->descs.clear(); cs->builds.clear(); cs->buildSlots.clear(); cs->ibuilds.clear(); cs->ibuildSlots.clear(); cs->stUsed = 0;
+  // (a resident image whose index was refused is resident no more: its slot takes a whole image next, not a delta)
+  if (badIndexed >= 0) cs->slots[badIndexed].res.on = false;
+  cs->descs.clear(); cs->builds.clear(); cs->buildSlots.clear(); cs->ibuilds.clear(); cs->ibuildSlots.clear(); cs->deltas.clear(); cs->stUsed = 0;
   for (t4_cellstore::Slot &sl : cs->slots) sl.pending = false;
   if (badSlot != -1) {   // the store goes on; that slot's table is incomplete until its cell is staged again
     (void)cellFlushPatches(cs);
@@ -2815,6 +2847,9 @@ int t4_cellstore_create(t4_ctx *c, int k, t4_cellstore **out) {
   cs->ctx = c; cs->k = k;
   double kmerHitProb = pow(0.8, k);  // SeqSet::ComputeNomatchGapLimit (SeqSet.hpp:2476-2482)
   cs->nomatchGapLimit = int(k * (log(0.01) / log(1 - kmerHitProb))) + 1;
+#ifdef T4_TEST_KNOBS
+  cs->dropFirstTouched = getenv("T4_TEST_DELTA_DROP") != nullptr && atoi(getenv("T4_TEST_DELTA_DROP")) != 0;
+#endif
   *out = cs;
   return T4_OK;
 }
@@ -2957,7 +2992,7 @@ int cellStage(t4_cellstore *cs, bool compact, int slot, int barcode, int nseq, c
       if ((r = cellAlloc(cs, cap, &p))) { sl.pending = false; return r; }   // (nothing of it is staged: the caller may stage the slot again)
       sl.base = p; sl.cap = cap;
     }
-    slotBase = sl.base; sl.imgBytes = blobBytes;
+    slotBase = sl.base; sl.imgBytes = blobBytes; sl.res.on = false;   // (an image of another form: the resident layout is gone)
     if (slot >= cs->viewCap || cs->stUsed + stagedBlob + viewBytes > cs->stCap)
       return fail(c, T4_ERR_STATE, "t4_cellstore_stage without a sufficient t4_cellstore_prepare (slot %d, %zu bytes)", slot, stagedBlob + viewBytes);
     stOff = cs->stUsed;
@@ -2972,7 +3007,7 @@ int cellStage(t4_cellstore *cs, bool compact, int slot, int barcode, int nseq, c
       d0.srcOff = stOff + headBytes; d0.dst = slotBase + oSeq; d0.bytes = blobBytes - oSeq;
       T4IndexBuild ib; ib.table = (T4HashEntC *)(slotBase + oHt); ib.post = (int2 *)(slotBase + oPost); ib.tableSlots = sz;
       ib.cntOff = stOff; ib.seqOff = stOff + headBytes; ib.consOff = stOff + headBytes + (oCons - oSeq);
-      ib.consBytes = (unsigned)consBytes; ib.npost = (unsigned)npost; ib.nseq = nseq; ib.k = cs->k;
+      ib.consBytes = (unsigned)consBytes; ib.npost = (unsigned)npost; ib.nseq = nseq; ib.k = cs->k; ib.src = nullptr;
       cs->ibuilds.push_back(ib); cs->ibuildSlots.push_back(slot);
     }
     T4CopyDesc d1; d1.srcOff = stOff + stagedBlob; d1.dst = (unsigned char *)(cs->dViews + slot); d1.bytes = viewBytes;
@@ -3067,6 +3102,202 @@ int t4_cellstore_stage_indexed(t4_cellstore *cs, int slot, int barcode, int nseq
 int t4_cellstore_indexed_stats(const t4_cellstore *cs, int64_t *out4) {
   if (!cs || !out4) return T4_ERR_ARG;
   out4[0] = cs->imagesIndexed; out4[1] = cs->countBytesShipped; out4[2] = cs->postingsIndexed; out4[3] = cs->tableBytesIndexed;
+  return T4_OK;
+}
+
+}  // extern "C"
+
+// ---- the resident form: the image stays in its slot, a change travels as the contigs it touched ---------------------------------
+namespace {
+inline size_t residentTableSlots(int64_t npost) {   // distinct keys <= postings: the table that serves npost keys at a load of 2/3
+  size_t sz = 64;
+  while (2 * sz < 3 * (size_t)npost + 2) sz <<= 1;
+  return sz;
+}
+inline size_t residentStretch(size_t len) { return (len + 1 + 64 + 127) & ~(size_t)127; }   // room for 64 more bases, in units of 128
+// 0: the delta fits the slot's resident layout; 1: it does not (a contig beyond its stretch, more contigs than records or than the
+// stretches have room for, more postings than the table serves); -1: it is no delta of this image at all (reason in *why)
+int residentFits(const t4_cellstore::Resident &rs, int nseq, int nTouched, const int32_t *ids, const int32_t *lens, int64_t npost, const char **why) {
+  if (!rs.on) { *why = "the slot holds no resident image"; return -1; }
+  if (nseq < rs.nseq) { *why = "fewer contigs than the resident image has"; return -1; }
+  int fresh = 0;
+  size_t used = rs.stretchUsed;
+  for (int j = 0; j < nTouched; ++j) {
+    const int id = ids[j];
+    if (id < 0 || id >= nseq) { *why = "a touched contig id outside the cell"; return -1; }
+    if (j > 0 && id <= ids[j - 1]) { *why = "touched contig ids not in ascending order"; return -1; }
+    if (lens[j] < 0) { *why = "a negative contig length"; return -1; }
+    if (id >= rs.nseq) { ++fresh; used += residentStretch((size_t)lens[j]); }
+  }
+  if (fresh != nseq - rs.nseq) { *why = "a new contig that is not among the touched ones"; return -1; }
+  if (nseq > rs.seqCap || used > rs.stretchCap || npost > (int64_t)rs.postCap) return 1;
+  for (int j = 0; j < nTouched; ++j) if (ids[j] < rs.nseq && (size_t)lens[j] + 1 > rs.cap[ids[j]]) return 1;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+// staged bytes of n contigs of the resident form, whole image or delta alike, exact: their records, three blocks of len + 1 bytes
+// rounded up to 16 for each, the view
+size_t t4_cellstore_resident_image_bytes(int n, const int32_t *lens) {
+  auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  size_t sz = al16(sizeof(T4DeltaRec) * (size_t)(n > 0 ? n : 0));
+  for (int j = 0; j < n; ++j) sz += 3 * al16((size_t)(lens[j] > 0 ? lens[j] : 0) + 1);
+  return sz + al16(sizeof(T4IndexView));
+}
+int t4_cellstore_delta_fits(t4_cellstore *cs, int slot, int nseq, int n_touched, const int32_t *touched_ids, const int32_t *lens, int64_t npost) {
+  if (!cs || slot < 0 || slot >= (int)cs->slots.size() || n_touched < 0 || (n_touched > 0 && (!touched_ids || !lens))) return 0;
+  const char *why = nullptr;
+  return residentFits(cs->slots[slot].res, nseq, n_touched, touched_ids, lens, npost, &why) == 0 ? 1 : 0;
+}
+int t4_cellstore_stage_delta(t4_cellstore *cs, int slot, int barcode, int nseq, int n_touched, const int32_t *touched_ids, const char *const *names,
+                             const char *const *cons, const int32_t *const *pw, const uint8_t *const *postCnt, const int32_t *postCntLen,
+                             int64_t npost, int64_t *pwOffsets) {
+  if (!cs || slot < 0 || slot >= (int)cs->slots.size() || !cs->slots[slot].live || nseq < 0 || npost < 0) return T4_ERR_ARG;
+  t4_ctx *c = cs->ctx;
+  (void)hipSetDevice(c->device);
+  const bool whole = n_touched < 0;
+  const int nT = whole ? nseq : n_touched;
+  if (nT > 0 && (!names || !cons || !pw || (!whole && !touched_ids))) return T4_ERR_ARG;
+  if (nseq > T4_MAX_SEQS) return fail(c, T4_ERR_UNSUPPORTED, "more than %d sequences in one barcode", T4_MAX_SEQS);
+  if (npost > 0xFFFFFFFFll) return fail(c, T4_ERR_ARG, "a resident image of %lld postings", (long long)npost);
+  auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  std::vector<int32_t> lens((size_t)nT), ids((size_t)nT);
+  std::vector<int64_t> sums((size_t)nT, 0);
+  for (int j = 0; j < nT; ++j) {
+    const size_t l = strlen(cons[j]);
+    if (l > T4_MAX_SEQLEN) return fail(c, T4_ERR_UNSUPPORTED, "contig longer than %d", T4_MAX_SEQLEN);
+    lens[j] = (int32_t)l; ids[j] = whole ? j : touched_ids[j];
+    if (!postCnt || !postCnt[j]) continue;
+    const int n = postCntLen ? postCntLen[j] : (int)l;
+    for (int o = 0; o < n; ++o) {
+      if (!postCnt[j][o]) continue;
+      if (o + cs->k > (int)l) return fail(c, T4_ERR_ARG, "postings counted at offset %d of contig %d, which has %d bases (k = %d)", o, ids[j], (int)l, cs->k);
+      sums[j] += postCnt[j][o];
+    }
+  }
+  const size_t viewBytes = al16(sizeof(T4IndexView)), recBytes = al16(sizeof(T4DeltaRec) * (size_t)nT);
+  size_t staged = recBytes;
+  for (int j = 0; j < nT; ++j) staged += 3 * al16((size_t)lens[j] + 1);
+  unsigned char *b = nullptr, *slotBase = nullptr;
+  size_t stOff = 0;
+  int r, dropped = 0;   // (records the test knob keeps back: the kernel's offsets count from the first record it is given)
+  {
+    std::lock_guard<std::mutex> lock(cs->mu);
+    t4_cellstore::Slot &sl = cs->slots[slot];
+    t4_cellstore::Resident &rs = sl.res;
+    const bool wasResident = rs.on;
+    if (sl.pending) return fail(c, T4_ERR_STATE, "slot %d already has an image staged for the next launch", slot);
+    int64_t total = 0;
+    for (int j = 0; j < nT; ++j) total += sums[j];
+    // (asked before the layout or a counter moves: a refusal leaves the slot as it was)
+    const bool room = slot < cs->viewCap && cs->stUsed + staged + viewBytes <= cs->stCap;
+    if (!whole) {   // refused before anything is queued or the layout is touched
+      const char *why = nullptr;
+      const int fit = residentFits(rs, nseq, nT, ids.data(), lens.data(), npost, &why);
+      if (fit < 0) return fail(c, T4_ERR_ARG, "the delta of slot %d: %s", slot, why);
+      for (int i = 0; i < rs.nseq; ++i) total += rs.cntSum[(size_t)i];
+      for (int j = 0; j < nT; ++j) if (ids[j] < rs.nseq) total -= rs.cntSum[(size_t)ids[j]];
+      if (total != npost) return fail(c, T4_ERR_ARG, "the counts of the image of slot %d add up to %lld postings, %lld were announced", slot, (long long)total, (long long)npost);
+      if (fit > 0) { ++cs->deltaMisfits; return T4_CELL_DELTA_WHOLE; }
+      if (!room) return fail(c, T4_ERR_STATE, "t4_cellstore_stage_delta without a sufficient t4_cellstore_prepare (slot %d, %zu bytes)", slot, staged + viewBytes);
+    } else {
+      if (total != npost) return fail(c, T4_ERR_ARG, "the counts of the image of slot %d add up to %lld postings, %lld were announced", slot, (long long)total, (long long)npost);
+      // a fresh layout: spare records and spare stretch room for contigs to come
+      t4_cellstore::Resident nr;
+      nr.tableSlots = residentTableSlots(npost); nr.postCap = (2 * nr.tableSlots - 2) / 3;
+      nr.seqCap = (nseq + 8 + 7) & ~7; nr.nseq = 0;
+      size_t used = 0;
+      for (int j = 0; j < nseq; ++j) used += residentStretch((size_t)lens[j]);
+      nr.stretchCap = used + (size_t)(nr.seqCap - nseq) * 256;
+      if (nr.stretchCap > 0x7FFFFFFFull) return fail(c, T4_ERR_UNSUPPORTED, "the contigs of one barcode exceed 2 GB");
+      if (!room) return fail(c, T4_ERR_STATE, "t4_cellstore_stage_delta without a sufficient t4_cellstore_prepare (slot %d, %zu bytes)", slot, staged + viewBytes);
+      nr.oPost = sizeof(T4HashEntC) * nr.tableSlots; nr.oSeq = al16(nr.oPost + sizeof(int2) * nr.postCap);
+      nr.oPw = (nr.oSeq + sizeof(T4SeqInfo) * (size_t)nr.seqCap + 127) & ~(size_t)127; nr.oCons = nr.oPw + nr.stretchCap; nr.oCnt = nr.oCons + nr.stretchCap;
+      const size_t blobBytes = nr.oCnt + nr.stretchCap + 16;
+      if (blobBytes > sl.cap) {
+        if (sl.base) cs->freeBySize[sl.cap].push_back(sl.base);
+        size_t cap = (size_t)64 << 10;
+        while (cap < blobBytes + blobBytes / 2) cap <<= 1;
+        sl.base = nullptr; sl.cap = 0; sl.imgBytes = 0; rs.on = false;
+        unsigned char *p = nullptr;
+        if ((r = cellAlloc(cs, cap, &p))) return r;
+        sl.base = p; sl.cap = cap;
+      }
+      if (wasResident) ++cs->residentRestages;
+      sl.imgBytes = blobBytes;
+      rs = std::move(nr); rs.on = true;
+    }
+    sl.pending = true;
+    slotBase = sl.base;
+    stOff = cs->stUsed;
+    b = cs->stHost.p + stOff;
+    cs->stUsed += staged + viewBytes;
+    // the layout takes the touched contigs: new ones get the next stretches, in the order of their ids
+    rs.off.resize((size_t)nseq); rs.cap.resize((size_t)nseq); rs.len.resize((size_t)nseq); rs.cntSum.resize((size_t)nseq, 0);
+    for (int j = 0; j < nT; ++j) {
+      const size_t id = (size_t)ids[j];
+      if ((int)id >= rs.nseq) { rs.off[id] = (uint32_t)rs.stretchUsed; rs.cap[id] = (uint32_t)residentStretch((size_t)lens[j]); rs.stretchUsed += rs.cap[id]; }
+      rs.len[id] = (uint32_t)lens[j]; rs.cntSum[id] = sums[j];
+    }
+    rs.nseq = nseq;
+#ifdef T4_TEST_KNOBS
+    if (!whole && cs->dropFirstTouched && nT > 0) dropped = 1;   // (the record and payload of the first touched contig stay behind)
+#endif
+    const int nShip = nT - dropped;
+    T4DeltaApply da;
+    da.seqs = (T4SeqInfo *)(slotBase + rs.oSeq); da.pw = slotBase + rs.oPw; da.cons = slotBase + rs.oCons; da.cnt = slotBase + rs.oCnt;
+    da.view = cs->dViews + slot; da.recOff = stOff + (size_t)dropped * sizeof(T4DeltaRec); da.viewOff = stOff + staged; da.nTouched = nShip; da.pad = 0;
+    cs->deltas.push_back(da);
+    T4IndexBuild ib; ib.table = (T4HashEntC *)slotBase; ib.post = (int2 *)(slotBase + rs.oPost); ib.tableSlots = rs.tableSlots;
+    ib.cntOff = rs.oCnt; ib.seqOff = rs.oSeq; ib.consOff = rs.oCons; ib.consBytes = (unsigned)rs.stretchUsed; ib.npost = (unsigned)npost;
+    ib.nseq = nseq; ib.k = cs->k; ib.src = slotBase;
+    cs->ibuilds.push_back(ib); cs->ibuildSlots.push_back(slot);
+    if (whole) ++cs->residentWhole; else { ++cs->residentDeltas; cs->deltaContigs += nT; }
+  }
+  // (from here on the slot's layout record is read only: stage calls of other slots may run beside this one)
+  const t4_cellstore::Resident &rs = cs->slots[slot].res;
+  memset(b, 0, staged + viewBytes);
+  T4DeltaRec *recs = (T4DeltaRec *)b;
+  size_t at = recBytes;
+  int maxLen = 0;
+  for (int j = 0; j < nT; ++j) {
+    const size_t id = (size_t)ids[j], l = (size_t)lens[j], bytes = al16(l + 1);
+    T4DeltaRec &rc = recs[j];
+    T4SeqInfo &f = rc.info;
+    f.consOff = (int)rs.off[id]; f.len = (int)l; f.pwOff = (int)rs.off[id]; f.barcode = barcode; f.isRef = 0; f.pad1 = 0;
+    char nm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    strncpy(nm, names[j], 7);
+    const int gt = geneType(nm);
+    f.geneType = gt < 0 ? 255 : (unsigned char)gt;
+    f.name0 = (unsigned char)nm[0]; f.name1 = (unsigned char)nm[1]; f.name2 = (unsigned char)nm[2]; f.name3 = (unsigned char)nm[3];
+    rc.seq = (int)id; rc.srcOff = (unsigned)(at - (size_t)dropped * sizeof(T4DeltaRec)); rc.bytes = (unsigned)bytes; rc.cap = rs.cap[id];
+    T4PW *pwOut = (T4PW *)(b + at);
+    if (l > 0 && pw[j]) for (size_t t = 0; t < l; ++t) pwOut[t] = t4PwByte(pw[j][4 * t], pw[j][4 * t + 1], pw[j][4 * t + 2], pw[j][4 * t + 3]);
+    for (size_t t = (l > 0 && pw[j]) ? l : 0; t < bytes; ++t) pwOut[t] = t4PwByte(0, 0, 0, 0);
+    memcpy(b + at + bytes, cons[j], l);
+    size_t n = (postCnt && postCnt[j]) ? (postCntLen ? (size_t)(postCntLen[j] > 0 ? postCntLen[j] : 0) : l) : 0;
+    if (n > l) n = l;
+    if (n) memcpy(b + at + 2 * bytes, postCnt[j], n);
+    at += 3 * bytes;
+  }
+  for (int i = 0; i < nseq; ++i) if ((int)rs.len[(size_t)i] > maxLen) maxLen = (int)rs.len[(size_t)i];
+  if (pwOffsets) for (int i = 0; i < nseq; ++i) pwOffsets[i] = (int64_t)(rs.oPw + rs.off[(size_t)i]);
+  T4IndexView &v = *(T4IndexView *)(b + staged);
+  v.k = cs->k; v.nseq = nseq; v.direct = 2; v.considerBarcode = 1;
+  v.hashMask = rs.tableSlots - 1; v.table = nullptr; v.htab = nullptr; v.ctab = (const T4HashEntC *)slotBase; v.post = (const int2 *)(slotBase + rs.oPost);
+  v.seqs = (const T4SeqInfo *)(slotBase + rs.oSeq); v.cons = (const char *)(slotBase + rs.oCons); v.pw = (const T4PW *)(slotBase + rs.oPw);
+  v.radius = cs->radius; v.hitLenRequired = cs->hitLenRequired; v.nomatchGapLimit = cs->nomatchGapLimit;
+  v.firstIsRef = 0; v.hasNovel = 2;
+  v.key32 = t4Key32Bits(nseq, maxLen);
+  v.novelSim = cs->novelSim; v.refSim = 0.75; v.repeatSim = 0.95;
+  return T4_OK;
+}
+int t4_cellstore_resident_stats(const t4_cellstore *cs, int64_t *out7) {
+  if (!cs || !out7) return T4_ERR_ARG;
+  out7[0] = cs->residentWhole; out7[1] = cs->residentDeltas; out7[2] = cs->deltaContigs; out7[3] = cs->deltaMisfits;
+  out7[4] = cs->residentRestages; out7[5] = cs->postingsResident; out7[6] = cs->tableBytesResident;
   return T4_OK;
 }
 

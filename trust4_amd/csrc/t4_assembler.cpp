@@ -380,6 +380,7 @@ struct Seq {
   // live set: place in the device arena of consensus chars / predicate bytes, and what of it changed since the last delta
   int64_t baseOff = -1; int baseCap = 0;
   bool devDirty = false; int dLo = 0, dHi = 0;
+  bool resTouched = false;   // cell in the resident image form: on the list of contigs the next delta ships (t4_assembler::touch)
 };
 
 struct Ov {  // struct _overlap fields that the Add path reads or writes
@@ -839,8 +840,15 @@ struct t4_assembler : IndexListener {
   // a cell's counts (the indexed image form ships them, stageImage; kept only for a cell set in that form): the same bytes, no dirty
   // marks; a count that would pass 255 cannot be shipped as a byte, and the cell stages compact images from then on
   bool keepCounts = false, countsOverflowed = false;
+  // the resident image form (stageImage): the contigs whose consensus, predicate bytes, name or counts changed since the last image;
+  // residentWhole: the next image travels whole (no image yet, the slot was given up, contigs were renumbered)
+  std::vector<int32_t> touched;
+  bool trackTouched = false, residentWhole = true, planWhole = true;
+  int64_t planStamp = -1;   // the owner's batch planResident last ran in: stageImage plans for itself when that is not the current one
+  void touch(int i) { if (trackTouched && i >= 0 && i < (int)seqs.size() && !seqs[i].resTouched) { seqs[i].resTouched = true; touched.push_back(i); } }
   void cellCount(int idx, int off, int delta) {
     if (!keepCounts || idx < 0 || idx >= (int)seqs.size() || off < 0) return;
+    touch(idx);
     Seq &q = seqs[idx];
     if ((int)q.postCnt.size() <= off) q.postCnt.resize((size_t)off + 64, 0);
     uint8_t &v = q.postCnt[(size_t)off];
@@ -880,6 +888,7 @@ struct t4_assembler : IndexListener {
   // contig c changed in a way a query can observe (consensus, length, postings, an IsBaseEqual state of a column).
   // fine == true: the caller described the change to the window itself (evRegion / evShift)
   void structuralChange(int c, bool fine = false) {
+    if (trackTouched) { touch(c); for (const PwPatch &pp : patches) touch(pp.seq); }   // (a byte patch that is dropped here travels with its contig)
     dirty = true; patches.clear();
     if (live()) { markSeqDirty(c); if (!fine) evContig(c); }
     else invalidateCell();
@@ -967,6 +976,9 @@ struct t4_assembler : IndexListener {
     for (const auto &kv : index.map)
       for (uint32_t t = 0; t < kv.second.cnt; ++t) cellCount(index.arena[kv.second.start + t].idx, index.arena[kv.second.start + t].offset, +1);
   }
+  bool residentImage();   // cell mode: this cell's next image goes in the resident form, whole or as a delta
+  size_t planResident();  // ... which of the two, and the bytes it stages (serial, ahead of t4_cellstore_prepare)
+  bool countsMatchIndex(const std::vector<const uint8_t *> &cnt, const std::vector<int32_t> &cntLen) const;
   bool indexedImage();   // cell mode: this cell's next image goes in the indexed form (the owner asked for it, no count outgrew its byte)
   int stageImage();   // cell mode: queue this cell's image in the owner's arena
   int releaseFinishedBarcode(int barcode, int contigMinCov);
@@ -1099,7 +1111,7 @@ struct t4_assembler : IndexListener {
       liveReset = true; baseUsed = 0; dirtySeqs.clear(); maxSeqLenSeen = 0;
       for (int i = 0; i < (int)seqs.size(); ++i) { seqs[i].baseOff = -1; seqs[i].baseCap = 0; seqs[i].devDirty = false; markSeqDirty(i); }
     }
-    dirty = true;
+    dirty = true; residentWhole = true;   // (the contigs were renumbered)
     return T4_OK;
   }
   int addRead(const char *read, const char *geneName, int *strandIO, int barcode, int minKmerCount, bool repetitiveData, double similarityThreshold);
@@ -1503,6 +1515,44 @@ bool t4_assembler::indexedImage() {
   if (countsOverflowed && !fallbackCounted) { fallbackCounted = true; ++owner->fallbackCells; }
   return !countsOverflowed;
 }
+bool t4_assembler::residentImage() {
+  if (!owner || owner->imageForm != T4_CELL_IMAGE_RESIDENT) return false;
+  if (countsOverflowed && !fallbackCounted) { fallbackCounted = true; ++owner->fallbackCells; }
+  return !countsOverflowed;
+}
+size_t t4_assembler::planResident() {
+  planStamp = owner->batchSeq;
+  for (const PwPatch &pp : patches) touch(pp.seq);   // (the image drops the pending byte patches: they travel with their contigs)
+  std::sort(touched.begin(), touched.end());
+  std::vector<int32_t> lens;
+  auto lenOf = [&](int i) { return seqs[i].released ? 0 : (int32_t)seqs[i].cons.size(); };
+  planWhole = residentWhole || touched.empty() || slot < 0;
+  if (!planWhole) {
+    for (int32_t i : touched) lens.push_back(lenOf(i));
+    planWhole = t4_cellstore_delta_fits(owner->store, slot, (int)seqs.size(), (int)touched.size(), touched.data(), lens.data(), (int64_t)index.total) != 1;
+  }
+  if (planWhole) { lens.clear(); for (int i = 0; i < (int)seqs.size(); ++i) lens.push_back(lenOf(i)); }
+  return t4_cellstore_resident_image_bytes((int)lens.size(), lens.data());
+}
+// T4_TEST_IMAGE_CROSSCHECK: the maintained counts (cnt[i], cntLen[i] of contig i) against the ones the map gives
+bool t4_assembler::countsMatchIndex(const std::vector<const uint8_t *> &cnt, const std::vector<int32_t> &cntLen) const {
+  const int n = (int)seqs.size();
+  std::vector<std::vector<int>> want(n);
+  for (int i = 0; i < n; ++i) want[i].assign(seqs[i].released ? 0 : seqs[i].cons.size() + 1, 0);
+  bool ok = true;
+  for (const auto &kv : index.map)
+    for (uint32_t t = 0; t < kv.second.cnt; ++t) {
+      const Post &p = index.arena[kv.second.start + t];
+      if (p.idx < 0 || p.idx >= n || p.offset < 0 || (size_t)p.offset >= want[p.idx].size()) { ok = false; continue; }
+      ++want[p.idx][(size_t)p.offset];
+    }
+  for (int i = 0; i < n && ok; ++i) {
+    for (size_t o = 0; o < want[i].size() && ok; ++o) ok = want[i][o] == ((int)o < cntLen[i] ? (int)cnt[i][o] : 0);
+    // (counts kept beyond what is shipped must be zeros)
+    if (!seqs[i].released) for (size_t o = (size_t)cntLen[i]; o < seqs[i].postCnt.size() && ok; ++o) ok = seqs[i].postCnt[o] == 0;
+  }
+  return ok;
+}
 int t4_assembler::stageImage() {   // thread-safe across cells once the owner has run t4_cellstore_prepare
   if (!dirty) return T4_OK;
   int r;
@@ -1517,6 +1567,46 @@ int t4_assembler::stageImage() {   // thread-safe across cells once the owner ha
     cons[i] = gone ? "" : q.cons.c_str();
     pw[i] = (gone || q.pw.empty()) ? nullptr : (const int32_t *)q.pw.data();
   }
+  if (residentImage()) {   // the image is in its slot: only the touched contigs travel (all of them when it goes whole), table and postings are rebuilt there
+    if (planStamp != owner->batchSeq) (void)planResident();   // (not planned in this batch: the plan of an earlier one says nothing about the slot as it is)
+    std::vector<const uint8_t *> cnt(n);
+    std::vector<int32_t> cntLen(n);
+    for (int i = 0; i < n; ++i) {
+      const Seq &q = seqs[i];
+      cnt[i] = (q.released || q.postCnt.empty()) ? nullptr : q.postCnt.data();
+      cntLen[i] = cnt[i] ? (int32_t)std::min(q.postCnt.size(), q.cons.size()) : 0;
+    }
+#ifdef T4_TEST_KNOBS
+    if (owner->crosscheck) {
+      if (!countsMatchIndex(cnt, cntLen)) { fprintf(stderr, "t4_assembler: the posting counts of cell %d differ from its index\n", cellBarcode); return T4_ERR_STATE; }
+      ++owner->imagesCrosschecked;
+    }
+#endif
+    imgPwOff.resize(n);
+    if (planWhole) r = t4_cellstore_stage_delta(owner->store, slot, cellBarcode, n, -1, nullptr, names.data(), cons.data(), pw.data(), cnt.data(), cntLen.data(), (int64_t)index.total, imgPwOff.data());
+    else {
+      const int nt = (int)touched.size();
+      std::vector<const char *> tn(nt), tc(nt);
+      std::vector<const int32_t *> tp(nt);
+      std::vector<const uint8_t *> tcnt(nt);
+      std::vector<int32_t> tlen(nt);
+      for (int j = 0; j < nt; ++j) { const int i = touched[j]; tn[j] = names[i]; tc[j] = cons[i]; tp[j] = pw[i]; tcnt[j] = cnt[i]; tlen[j] = cntLen[i]; }
+      r = t4_cellstore_stage_delta(owner->store, slot, cellBarcode, n, nt, touched.data(), tn.data(), tc.data(), tp.data(), tcnt.data(), tlen.data(), (int64_t)index.total, imgPwOff.data());
+      if (r == T4_CELL_DELTA_WHOLE) return T4_ERR_STATE;   // (planResident asked the store: cannot happen)
+    }
+    if (r) return r;
+    for (int32_t i : touched) seqs[i].resTouched = false;
+    touched.clear(); residentWhole = false;
+    patches.clear();
+    dirty = false; ++refreshes;
+    ++owner->stagedImages;
+    return T4_OK;
+  }
+  if (!touched.empty()) {   // (an image of another form ships every contig)
+    for (int32_t i : touched) seqs[i].resTouched = false;
+    touched.clear();
+  }
+  residentWhole = true;
   if (indexedImage()) {   // the index travels as the contigs' counts: the map is not walked
     std::vector<const uint8_t *> cnt(n);
     std::vector<int32_t> cntLen(n);
@@ -1526,22 +1616,8 @@ int t4_assembler::stageImage() {   // thread-safe across cells once the owner ha
       cntLen[i] = cnt[i] ? (int32_t)std::min(q.postCnt.size(), q.cons.size()) : 0;
     }
 #ifdef T4_TEST_KNOBS
-    if (owner->crosscheck) {   // T4_TEST_IMAGE_CROSSCHECK: the maintained counts against the ones the map gives
-      std::vector<std::vector<int>> want(n);
-      for (int i = 0; i < n; ++i) want[i].assign(seqs[i].released ? 0 : seqs[i].cons.size() + 1, 0);
-      bool ok = true;
-      for (const auto &kv : index.map)
-        for (uint32_t t = 0; t < kv.second.cnt; ++t) {
-          const Post &p = index.arena[kv.second.start + t];
-          if (p.idx < 0 || p.idx >= n || p.offset < 0 || (size_t)p.offset >= want[p.idx].size()) { ok = false; continue; }
-          ++want[p.idx][(size_t)p.offset];
-        }
-      for (int i = 0; i < n && ok; ++i) {
-        for (size_t o = 0; o < want[i].size() && ok; ++o) ok = want[i][o] == ((int)o < cntLen[i] ? (int)cnt[i][o] : 0);
-        // (counts kept beyond what is shipped must be zeros)
-        if (!seqs[i].released) for (size_t o = (size_t)cntLen[i]; o < seqs[i].postCnt.size() && ok; ++o) ok = seqs[i].postCnt[o] == 0;
-      }
-      if (!ok) { fprintf(stderr, "t4_assembler: the posting counts of cell %d differ from its index\n", cellBarcode); return T4_ERR_STATE; }
+    if (owner->crosscheck) {
+      if (!countsMatchIndex(cnt, cntLen)) { fprintf(stderr, "t4_assembler: the posting counts of cell %d differ from its index\n", cellBarcode); return T4_ERR_STATE; }
       ++owner->imagesCrosschecked;
     }
 #endif
@@ -3106,7 +3182,7 @@ bool t4_assembler::isContigShallow(int i, int minCov) const {
 }
 // SeqSet::ReleaseShallowContigs (SeqSet.hpp:10926-10936): at the end of the run, the index is not touched any more
 void t4_assembler::releaseShallowContigs(int minCov) {
-  for (int i = 0; i < (int)seqs.size(); ++i) if (isContigShallow(i, minCov)) { seqs[i].released = true; dirty = true; }
+  for (int i = 0; i < (int)seqs.size(); ++i) if (isContigShallow(i, minCov)) { seqs[i].released = true; dirty = true; touch(i); }
 }
 
 // SeqSet::ReleaseFinishedBarcodeSeq({barcode}, removeFromIndex = true, contigMinCov, earlyStop = true)
@@ -3305,6 +3381,15 @@ int t4_assembler_change_kmer_length(t4_assembler *a, int kmer_length) {
   if (!a || kmer_length < 2 || kmer_length > 31) return T4_ERR_ARG;
   return a->changeKmerLength(kmer_length);
 }
+#ifdef T4_TEST_KNOBS
+int t4_assembler_test_index_again(t4_assembler *a, int seq_idx, int times) {
+  if (!a || seq_idx < 0 || seq_idx >= (int)a->seqs.size() || times < 0 || a->seqs[seq_idx].released) return T4_ERR_ARG;
+  const Seq &s = a->seqs[seq_idx];
+  for (int t = 0; t < times; ++t) a->index.build(s.cons.c_str(), (int)s.cons.size(), seq_idx, s.barcode, 0);
+  a->structuralChange(seq_idx);
+  return T4_OK;
+}
+#endif
 int64_t t4_assembler_index_postings(const t4_assembler *a) { return a ? (int64_t)a->index.total : 0; }
 int t4_assembler_release_finished_barcode(t4_assembler *a, int barcode, int contig_min_cov) {
   if (!a) return T4_ERR_ARG;
@@ -3360,7 +3445,7 @@ int t4_cellset_cell(t4_cellset *cs, int barcode, t4_assembler **cell) {
   if (it == cs->cells.end()) {
     t4_assembler *a = new t4_assembler(cs->ctx, cs->k);
     a->index.considerBarcode = true;
-    a->owner = cs; a->cellBarcode = barcode; a->keepCounts = cs->imageForm == T4_CELL_IMAGE_INDEXED;
+    a->owner = cs; a->cellBarcode = barcode; a->keepCounts = cs->imageForm != T4_CELL_IMAGE_COMPACT; a->trackTouched = cs->imageForm == T4_CELL_IMAGE_RESIDENT;
     a->hitLenRequired = cs->hitLenRequired; a->radius = cs->radius; a->novelSim = cs->novelSim;
     it = cs->cells.emplace(barcode, a).first;
   }
@@ -3370,7 +3455,7 @@ int t4_cellset_cell(t4_cellset *cs, int barcode, t4_assembler **cell) {
 int t4_cellset_close_cell(t4_cellset *cs, t4_assembler *cell) {   // no further queries for this cell: its arena slot is recycled
   if (!cs || !cell || cell->owner != cs) return T4_ERR_ARG;
   cell->dropWindow();
-  if (cell->slot >= 0) { int r = t4_cellstore_close(cs->store, cell->slot); cell->slot = -1; cell->dirty = true; return r; }
+  if (cell->slot >= 0) { int r = t4_cellstore_close(cs->store, cell->slot); cell->slot = -1; cell->dirty = true; cell->residentWhole = true; return r; }
   return T4_OK;
 }
 
@@ -3415,7 +3500,8 @@ int t4_cellset_prefetch(t4_cellset *cs, int n, t4_assembler *const *cells, const
     if (cell->dirty) {
       int64_t consBytes = 0;
       for (const Seq &q : cell->seqs) consBytes += (q.released ? 0 : (int64_t)q.cons.size()) + 1;
-      stageBytes += cell->indexedImage() ? t4_cellstore_indexed_image_bytes((int)cell->seqs.size(), consBytes)
+      stageBytes += cell->residentImage() ? cell->planResident()
+                    : cell->indexedImage() ? t4_cellstore_indexed_image_bytes((int)cell->seqs.size(), consBytes)
                                          : t4_cellstore_image_bytes((int)cell->seqs.size(), (int64_t)cell->index.map.size(), (int64_t)cell->index.total, consBytes);
     }
   }
@@ -3518,13 +3604,14 @@ int t4_cellset_counters(const t4_cellset *cs, int64_t *query_batches, int64_t *r
   return T4_OK;
 }
 int t4_cellset_set_image_form(t4_cellset *cs, int form) {
-  if (!cs || (form != T4_CELL_IMAGE_COMPACT && form != T4_CELL_IMAGE_INDEXED)) return T4_ERR_ARG;
+  if (!cs || (form != T4_CELL_IMAGE_COMPACT && form != T4_CELL_IMAGE_INDEXED && form != T4_CELL_IMAGE_RESIDENT)) return T4_ERR_ARG;
   if (cs->prefetched) return T4_ERR_STATE;
   cs->imageForm = form;
   for (auto &kv : cs->cells) {
     const bool was = kv.second->keepCounts;
-    kv.second->keepCounts = form == T4_CELL_IMAGE_INDEXED;
+    kv.second->keepCounts = form != T4_CELL_IMAGE_COMPACT; kv.second->trackTouched = form == T4_CELL_IMAGE_RESIDENT;
     if (kv.second->keepCounts && !was) kv.second->recount();
+    kv.second->residentWhole = true;
   }
   return T4_OK;
 }
@@ -3535,6 +3622,15 @@ int t4_cellset_indexed_stats(const t4_cellset *cs, int64_t *out, int n) {
   if (r) return r;
   v[4] = cs->fallbackCells.load(); v[5] = cs->imagesCrosschecked.load();
   for (int i = 0; i < n && i < 6; ++i) out[i] = v[i];
+  return T4_OK;
+}
+int t4_cellset_resident_stats(const t4_cellset *cs, int64_t *out, int n) {
+  if (!cs || !out || n < 0) return T4_ERR_ARG;
+  int64_t v[8];
+  int r = t4_cellstore_resident_stats(cs->store, v);
+  if (r) return r;
+  v[7] = cs->fallbackCells.load();
+  for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
   return T4_OK;
 }
 int64_t t4_cellset_live_keys_staged(const t4_cellset *cs) { return cs ? cs->stagedLiveKeys.load() : 0; }

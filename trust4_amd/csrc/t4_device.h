@@ -309,5 +309,15 @@ struct T4CopyDesc { unsigned long long srcOff; unsigned char *dst; unsigned long
 struct T4TableBuild { T4HashEntC *table; unsigned long long tableSlots, srcOff, nKeys; };   // table of a set image built on the device from nKeys staged (code, start, cnt) records
 // table AND postings of a set image built on the device from its contigs (cellIndexBuildKernel): the staged count bytes (one per
 // consensus byte, cntOff), sequence records (seqOff) and consensus block (consOff) of the image, all offsets into the staging buffer
-struct T4IndexBuild { T4HashEntC *table; int2 *post; unsigned long long tableSlots, cntOff, seqOff, consOff; unsigned consBytes, npost; int nseq, k; };
+// src == null: the three offsets are into the staging buffer (the indexed form). src != null: a resident image, whose count bytes,
+// records and consensus block lie in its slot -- offsets from src, the slot's base (cellDeltaApplyKernel has brought them up to date).
+struct T4IndexBuild { T4HashEntC *table; int2 *post; unsigned long long tableSlots, cntOff, seqOff, consOff; unsigned consBytes, npost; int nseq, k; const unsigned char *src; };
+// A resident image keeps, behind table, postings and records, three byte blocks of equal size -- predicate bytes,
+// consensus, count bytes -- in which contig i owns the same stretch [consOff(i), consOff(i) + cap(i)) (pwOff == consOff; cap a
+// multiple of 128, at least len + 1). A change travels as the contigs it touched: per contig one T4DeltaRec and `bytes` (len + 1
+// rounded up to 16, zeros behind the terminator) bytes of each block at srcOff, srcOff + bytes, srcOff + 2 * bytes from the
+// delta's first staged byte. cellDeltaApplyKernel copies them into the stretch, clears the count bytes up to cap, writes the
+// record and the view.
+struct T4DeltaRec { T4SeqInfo info; int seq; unsigned srcOff, bytes, cap; };
+struct T4DeltaApply { T4SeqInfo *seqs; unsigned char *pw, *cons, *cnt; T4IndexView *view; unsigned long long recOff, viewOff; int nTouched, pad; };
 enum { T4_IDXERR_KMER = 1 /* a counted offset without a whole ACGT k-mer */, T4_IDXERR_FULL = 2 /* no free table slot */, T4_IDXERR_TOTAL = 3 /* the counts do not add up to npost */ };

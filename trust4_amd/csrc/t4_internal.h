@@ -48,6 +48,38 @@ size_t t4_cellstore_indexed_image_bytes(int nseq, int64_t cons_bytes);   // stag
 // 4 values: images indexed on the device, count bytes shipped for them (padded), postings written on the device, table bytes
 // written on the device (16 per slot). t4_cellstore_image_stats' first three values do not count these images; its fourth does.
 int t4_cellstore_indexed_stats(const t4_cellstore *cs, int64_t *out4);
+// The resident form: the image stays in its slot between rounds and a change travels as the contigs it touched. The slot keeps
+// [table] [postings] [records] and three byte blocks of equal size -- predicate bytes, consensus, count bytes -- in which contig i owns
+// one stretch (room for 64 more bases, rounded up to a multiple of 128) that never moves; the table is sized from npost (distinct keys
+// <= postings, load <= 2/3, at least 64 slots), the postings have the room that table can serve, there are spare records and spare
+// stretch room for contigs to come. The flush runs cellDeltaApplyKernel (touched contigs into their stretches, their records, the view),
+// then cellIndexBuildKernel, which rebuilds table and postings from the contigs and counts as they lie in the slot.
+// n_touched < 0: the whole image -- names, cons, pw, post_cnt, post_cnt_len have nseq entries, the slot gets a fresh layout.
+// n_touched >= 0: a delta -- the arrays have n_touched entries, entry j for contig touched_ids[j] (ascending); a new contig and a
+// released one ("") are touched contigs, an untouched contig keeps everything including its counts; npost is the new total.
+// post_cnt as for t4_cellstore_stage_indexed. pw_offsets (nullable, nseq values): byte offset of every contig's predicate bytes in
+// the image, for t4_cellstore_patch. Returns T4_OK, or T4_CELL_DELTA_WHOLE with nothing queued: the delta does not fit the slot's
+// layout (a contig beyond its stretch, more contigs than records or stretch room, more postings than the table serves) and the cell
+// is to be staged whole. Refused with T4_ERR_ARG, nothing queued: a touched id out of range or out of order, a new contig that is
+// not touched, a count at o + k beyond the contig, counts that do not add up to npost, a delta for a slot without a resident image
+// (never staged whole, recycled, or staged in another form since). Refused by the flush as for the indexed form (a counted offset
+// whose k-mer has a letter outside ACGT); that slot then holds no resident image.
+#define T4_CELL_DELTA_WHOLE 1
+int t4_cellstore_stage_delta(t4_cellstore *cs, int slot, int barcode, int nseq, int n_touched, const int32_t *touched_ids,
+                             const char *const *names, const char *const *cons, const int32_t *const *pw, const uint8_t *const *post_cnt,
+                             const int32_t *post_cnt_len, int64_t npost, int64_t *pw_offsets);
+// staged size of n contigs of the given lengths in that form, whole image or delta alike, exact
+size_t t4_cellstore_resident_image_bytes(int n, const int32_t *lens);
+// 1: t4_cellstore_stage_delta would take this delta (lens[j]: bases of contig touched_ids[j]); 0: the cell is to be staged whole
+int t4_cellstore_delta_fits(t4_cellstore *cs, int slot, int nseq, int n_touched, const int32_t *touched_ids, const int32_t *lens, int64_t npost);
+#ifdef T4_TEST_KNOBS
+// Test builds only: the index of contig seq_idx is built `times` more times over the contig as it stands (every indexed offset gets
+// that many more equal postings) -- the only way to more than 255 postings at one offset in a few calls.
+int t4_assembler_test_index_again(t4_assembler *a, int seq_idx, int times);
+#endif
+// 7 values: images staged whole, deltas, contigs shipped by deltas, deltas refused with T4_CELL_DELTA_WHOLE, whole images of slots
+// that held a resident image already, postings and table bytes (16 per slot) written on the device for this form
+int t4_cellstore_resident_stats(const t4_cellstore *cs, int64_t *out7);
 // Overwrite posWeight predicate bytes of the slot's resident image (byte offsets as returned by the last stage + the
 // column's index); applied after the staged images of the same flush.
 int t4_cellstore_patch(t4_cellstore *cs, int slot, int n, const int64_t *byte_offsets, const unsigned char *values);

@@ -4416,6 +4416,32 @@ __global__ __launch_bounds__(256) void cellTableBuildKernel(const unsigned char 
   }
 }
 
+// The contigs a change touched, into their stretches of a resident image (T4DeltaApply, T4DeltaRec in t4_device.h). One workgroup
+// per image, one wavefront per touched contig: the staged predicate bytes, consensus and count bytes of the contig (`bytes` each, a
+// multiple of 16, zeros behind the terminator) go to consOff(i) of the three blocks in 16-byte units -- stretches and staged
+// payloads both start on multiples of 16 --, the count bytes from `bytes` up to the stretch's end become zeros (what a longer contig
+// left there must not be counted), the contig's record and the image's view are replaced. Nothing here reads what another wavefront
+// writes; cellIndexBuildKernel follows on the same stream.
+__global__ __launch_bounds__(256) void cellDeltaApplyKernel(const unsigned char *staging, const T4DeltaApply *delta, int nDelta) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int d = blockIdx.x; d < nDelta; d += gridDim.x) {
+    const T4DeltaApply da = delta[d];
+    const unsigned char *base = staging + da.recOff;
+    const T4DeltaRec *recs = (const T4DeltaRec *)base;
+    for (int t = wave; t < da.nTouched; t += 4) {
+      const T4DeltaRec rc = recs[t];
+      const unsigned units = rc.bytes >> 4, capUnits = rc.cap >> 4;
+      const uint4 *sPw = (const uint4 *)(base + rc.srcOff), *sCons = sPw + units, *sCnt = sCons + units;
+      uint4 *dPw = (uint4 *)(da.pw + rc.info.consOff), *dCons = (uint4 *)(da.cons + rc.info.consOff), *dCnt = (uint4 *)(da.cnt + rc.info.consOff);
+      for (unsigned u = lane; u < units; u += 64) { dPw[u] = sPw[u]; dCons[u] = sCons[u]; dCnt[u] = sCnt[u]; }
+      uint4 zero; zero.x = 0u; zero.y = 0u; zero.z = 0u; zero.w = 0u;
+      for (unsigned u = units + lane; u < capUnits; u += 64) dCnt[u] = zero;
+      if (lane < 6) ((int *)(da.seqs + rc.seq))[lane] = ((const int *)&recs[t].info)[lane];   // (T4SeqInfo: six words)
+    }
+    if (threadIdx.x < sizeof(T4IndexView) / 16) ((uint4 *)da.view)[threadIdx.x] = ((const uint4 *)(staging + da.viewOff))[threadIdx.x];
+  }
+}
+
 // Byte i of an image's count block counts the postings (s, o): s is the contig whose consensus holds byte i (the last one with
 // consOff <= i; every contig owns at least its terminator, so the offsets rise strictly), o = i - consOff(s). Their key is the code of
 // cons[s][o .. o + K) as expandHitsContig forms it -- 2 bits per base, first base most significant, masked to 2 K bits -- which is
@@ -4437,8 +4463,10 @@ __device__ __forceinline__ bool cellIndexKey(const T4SeqInfo *seqs, const char *
 // Table AND postings of freshly staged per-barcode set images, built where they live from the image's own contigs: every posting
 // (s, o) of a cell's index has the code of the contig's k-mer at o, so one count byte per consensus byte -- how many postings (s, o)
 // the index holds -- says all the index says, and the order inside a posting list is not observable (the hits are sorted). One
-// workgroup per image; everything is read from STAGING (the scatter of the same flush writes the slot after this kernel), the table
-// and the postings are written in the slot. Four phases, a fence and a barrier between them:
+// workgroup per image; everything is read from STAGING (the scatter of the same flush writes the slot after this kernel) or, for a
+// resident image, from the slot itself (cellDeltaApplyKernel of the same flush wrote it before this kernel: its contigs lie in
+// stretches with slack, whose count bytes behind the contig are zeros); the table and the postings are written in the slot. Four
+// phases, a fence and a barrier between them:
 //   clear  every table slot empty, (~0, 0, 0)
 //   count  per counted offset: probe from mix64(code) & mask, claim an empty slot by a compare-and-swap of its code or meet the same
 //          code (the same key: the normal case here), add the count byte to the slot's cnt
@@ -4459,9 +4487,10 @@ __global__ __launch_bounds__(256) void cellIndexBuildKernel(const unsigned char 
     for (unsigned long long i = threadIdx.x; i < ib.tableSlots; i += blockDim.x) slots[i] = empty;
     __threadfence();
     __syncthreads();
-    const unsigned *cntWords = (const unsigned *)(staging + ib.cntOff);   // (the count block is padded to 16 bytes with zeros)
-    const T4SeqInfo *seqs = (const T4SeqInfo *)(staging + ib.seqOff);
-    const char *cons = (const char *)(staging + ib.consOff);
+    const unsigned char *src = ib.src ? ib.src : staging;   // a resident image is read where it lies (T4IndexBuild)
+    const unsigned *cntWords = (const unsigned *)(src + ib.cntOff);   // (the count block is padded to 16 bytes with zeros)
+    const T4SeqInfo *seqs = (const T4SeqInfo *)(src + ib.seqOff);
+    const char *cons = (const char *)(src + ib.consOff);
     const unsigned nWords = (ib.consBytes + 3u) >> 2;
     const unsigned long long mask = ib.tableSlots - 1;
     for (unsigned w = threadIdx.x; w < nWords; w += blockDim.x) {

@@ -1293,7 +1293,8 @@ int main(int argc, char *argv[]) {
   if (firstReadLen / 2 < 31) { int l = firstReadLen / 2; if (l < 21) l = 21; hitLenRequired = l; }
   if (hasBarcode) hitLenRequired = 13;
   if (minHitLen != -1) hitLenRequired = minHitLen;
-  bool cellImagesIndexed = false;
+  int cellImageForm = T4_CELL_IMAGE_COMPACT;
+  const char *const cellImageFormNames[] = {"compact", "indexed", "resident"};
   const bool useCells = hasBarcode && !keepMissingBarcode;   // --keepNoBarcode: the index is not keyed by barcode, one set
   if (useCells) {
     if (barcodeIntToStr.size() >= 1000003) { fprintf(stderr, "trust4-hip: more than 1000002 barcodes are not supported.\n"); return EXIT_FAILURE; }
@@ -1321,10 +1322,11 @@ int main(int argc, char *argv[]) {
     }
     G = (int)cellSets.size();
     // T4_CELL_IMAGES=indexed: the cells' images travel without their index, which the device builds from the contigs
-    { const char *form = getenv("T4_CELL_IMAGES"); cellImagesIndexed = form && !strcmp(form, "indexed"); }
-    if (getenv("T4_TIMING")) fprintf(stderr, "trust4-hip: cell images in the %s form\n", cellImagesIndexed ? "indexed" : "compact");
+    // T4_CELL_IMAGES=resident: the images stay in their slots, a change travels as the contigs it touched
+    { const char *form = getenv("T4_CELL_IMAGES"); cellImageForm = form && !strcmp(form, "indexed") ? T4_CELL_IMAGE_INDEXED : form && !strcmp(form, "resident") ? T4_CELL_IMAGE_RESIDENT : T4_CELL_IMAGE_COMPACT; }
+    if (getenv("T4_TIMING")) fprintf(stderr, "trust4-hip: cell images in the %s form\n", cellImageFormNames[cellImageForm]);
     for (int g = 0; g < G; ++g) {
-      if (cellImagesIndexed && (rc = t4_cellset_set_image_form(cellSets[(size_t)g], T4_CELL_IMAGE_INDEXED))) die(cellCtxs[(size_t)g], "t4_cellset_set_image_form", rc);
+      if (cellImageForm != T4_CELL_IMAGE_COMPACT && (rc = t4_cellset_set_image_form(cellSets[(size_t)g], cellImageForm))) die(cellCtxs[(size_t)g], "t4_cellset_set_image_form", rc);
       t4_cellset_set_params(cellSets[(size_t)g], hitLenRequired, 10, 0.9);
       t4_cellset_set_threads(cellSets[(size_t)g], (threadCnt + G - 1) / G);
     }
@@ -1798,7 +1800,7 @@ int main(int argc, char *argv[]) {
   auto cellSlots = [&]() { int n = 0; for (t4_cellset *cs : cellSets) n += t4_cellset_size(cs); return n; };
   auto destroyCells = [&]() { for (size_t g = 0; g < cellSets.size(); ++g) { t4_cellset_destroy(cellSets[g]); if (g > 0) t4_destroy(cellCtxs[g]); } cellSets.clear(); };
   auto writeCellStats = [&]() {
-    int64_t qb = 0, rq = 0, im = 0, by = 0, built = 0, keyRecs = 0, tabBytes = 0, indexed = 0, cntBytes = 0, postBuilt = 0; double sq = 0, ss = 0;
+    int64_t qb = 0, rq = 0, im = 0, by = 0, built = 0, keyRecs = 0, tabBytes = 0, indexed = 0, cntBytes = 0, postBuilt = 0, resWhole = 0, resDeltas = 0, resContigs = 0, resRestages = 0, resPost = 0, resTabBytes = 0, idxTabBytes = 0; double sq = 0, ss = 0;
     for (t4_cellset *cs : cellSets) {   // counts: sums over the cell groups; seconds: sums too (the groups overlap in time)
       int64_t a = 0, b = 0, c = 0, d = 0; double e = 0, f = 0;
       t4_cellset_counters(cs, &a, &b, &c, &d, &e, &f);
@@ -1806,9 +1808,12 @@ int main(int argc, char *argv[]) {
       int64_t is[4] = {0, 0, 0, 0};
       t4_cellset_image_stats(cs, is, 4);
       built += is[0]; keyRecs += is[1]; tabBytes += is[2];
-      int64_t xs[3] = {0, 0, 0};
-      t4_cellset_indexed_stats(cs, xs, 3);
-      indexed += xs[0]; cntBytes += xs[1]; postBuilt += xs[2];
+      int64_t xs[4] = {0, 0, 0, 0};
+      t4_cellset_indexed_stats(cs, xs, 4);
+      indexed += xs[0]; cntBytes += xs[1]; postBuilt += xs[2]; idxTabBytes += xs[3];
+      int64_t rs[7] = {0, 0, 0, 0, 0, 0, 0};
+      t4_cellset_resident_stats(cs, rs, 7);
+      resWhole += rs[0]; resDeltas += rs[1]; resContigs += rs[2]; resRestages += rs[4]; resPost += rs[5]; resTabBytes += rs[6];
     }
     if (const char *sj = getenv("T4_STATS_JSON")) {
       FILE *fp = fopen(sj, "w");
@@ -1818,9 +1823,13 @@ int main(int argc, char *argv[]) {
         fprintf(fp, "}, \"rough_annotation\": {\"reads\": %lld, \"hits\": %lld, \"kernel_ms\": %.3f}, ", annotReads, annotHits, annotKernelMs);
         fprintf(fp, "\"cells\": {\"groups\": %d, \"query_batches\": %lld, \"reads_queried\": %lld, \"images_staged\": %lld, \"bytes_staged\": %lld, \"query_wall_s\": %.3f, \"stage_wall_s\": %.3f, "
                     "\"images_built_on_device\": %lld, \"key_records_shipped\": %lld, \"table_bytes_built_on_device\": %lld, "
-                    "\"image_form\": \"%s\", \"images_indexed_on_device\": %lld, \"count_bytes_shipped\": %lld, \"postings_built_on_device\": %lld}, ",
+                    "\"image_form\": \"%s\", \"images_indexed_on_device\": %lld, \"count_bytes_shipped\": %lld, \"postings_built_on_device\": %lld, "
+                    "\"images_resident_whole\": %lld, \"deltas\": %lld, \"delta_contigs_shipped\": %lld, \"whole_restages\": %lld, "
+                    "\"table_bytes_indexed_on_device\": %lld, \"postings_rebuilt_on_device\": %lld, \"table_bytes_rebuilt_on_device\": %lld}, ",
                 (int)cellSets.size(), (long long)qb, (long long)rq, (long long)im, (long long)by, sq, ss, (long long)built, (long long)keyRecs, (long long)tabBytes,
-                cellImagesIndexed ? "indexed" : "compact", (long long)indexed, (long long)cntBytes, (long long)postBuilt);
+                cellImageFormNames[cellImageForm], (long long)indexed, (long long)cntBytes, (long long)postBuilt,
+                (long long)resWhole, (long long)resDeltas, (long long)resContigs, (long long)resRestages,
+                (long long)idxTabBytes, (long long)resPost, (long long)resTabBytes);
         fprintf(fp, "\"contigs\": %d, \"assembled_reads\": %d}\n", cellSlots(), (int)assembledReadIdx.size());
         fclose(fp);
       }
