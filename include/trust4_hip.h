@@ -245,6 +245,31 @@ int t4_add_query(t4_index *ix, int n, const char *bases, const int64_t *offsets,
  * (hit on the minus strand / no hit / hit on the plus strand). Uses the set's hit_len_required. Only mode 0 is built. */
 int t4_has_hit(t4_index *ref, t4_batch *b, int mode, int32_t *out);
 
+/* FASTQ text on the device: a t4_batch straight from the bytes of a file, piece by piece. The device finds the
+ * lines, validates the records (four lines each), packs the reads and applies the extractor's low-complexity rule; the host gets
+ * one 32-bit offset and one byte per record. A piece's status (info[2]): 0 every record passed; else the first failing check of
+ * the lowest failing record (info[3]): 1 line 0 does not begin with '@'; 2 line 2 does not begin with '+'; 3 quality length !=
+ * sequence length; 4 the sequence line begins with '@', '>' or '+'; 5 a byte outside 33..126 in a sequence or quality line, or a
+ * '\r' anywhere in the record; 6 a read longer than the engine takes (384); 7 a sequence byte outside 'A'..'Z'; 8 (final piece
+ * only) 1-3 lines left over after the last whole record. With status 0 the text means the same to kseq's record model. */
+typedef struct t4_text t4_text;   /* pinned staging, device text, line table, per-record arrays: reused from piece to piece */
+int t4_text_create(t4_ctx *ctx, int64_t max_piece_bytes, t4_text **out);
+void t4_text_destroy(t4_text *tx);
+/* upload one piece and build its line table. info[0] = whole records in the piece, info[1] = bytes they take, info[2] = status
+ * (above; records are validated here), info[3] = first offending record or -1, info[4] = longest read. final_piece: a last line
+ * without its '\n' ends at nbytes (otherwise it is left to the next piece, like everything from info[1] on). */
+int t4_text_scan(t4_text *tx, const char *text, int64_t nbytes, int final_piece, int64_t info[5]);
+/* records [first, first + n) of the scanned piece as a batch (T4_READS_KMERS_ONLY coding); the batch also carries the
+ * low-complexity bytes. T4_ERR_ARG for a piece whose status is not 0. */
+int t4_text_batch(t4_text *tx, int64_t first, int64_t n, t4_batch **out);
+/* rec_start[n + 1] (offsets into the piece; the last one is where record first + n begins, or info[1]) and/or low_complexity[n];
+ * either may be NULL */
+int t4_text_records(t4_text *tx, int64_t first, int64_t n, uint32_t *rec_start, uint8_t *low_complexity);
+/* the stage-0 test of FastqExtractor.cpp:129-134, 516-519 for n reads (and their mates, or NULL): keep[i] = pass(read i) ||
+ * pass(mate i), pass = not low-complexity and HasHitInSet != 0. A low-complexity read is not queried, a mate only when its read
+ * did not pass. Batches of t4_reads_upload* carry no low-complexity bytes: their reads count as not low. */
+int t4_candidate_test(t4_index *ref, t4_batch *reads, t4_batch *mates, uint8_t *keep);
+
 /* AlignAlgo::IsMateOverlap (AlignAlgo.hpp:1027-1096; ProcessRead, main.cpp:292-330) for a batch of pairs: is a suffix of
  * `first` a prefix of `second` at exactly one offset (length-dependent identity threshold, optional tandem-repeat veto)?
  * Reads as concatenated ACGTN chars with n + 1 offsets each. out3[3*i..]: the function's return value (overlap size or

@@ -102,6 +102,11 @@ def _load():
         "t4_add_query_head": (I, [P, I, C.POINTER(I), C.POINTER(P), C.POINTER(I)]),
         "t4_add_query_arm_long_lists": (I, [P, I, P, P, P, I]),
         "t4_add_query_last_long_lists": (I, [P, C.POINTER(P), C.POINTER(I)]),
+        # FASTQ text on the device
+        "t4_text_create": (I, [P, L, C.POINTER(P)]), "t4_text_destroy": (None, [P]), "t4_text_scan": (I, [P, P, L, I, P]),
+        "t4_text_batch": (I, [P, L, L, C.POINTER(P)]), "t4_text_records": (I, [P, L, L, P, P]), "t4_candidate_test": (I, [P, P, P, P]),
+        # ... and its test aids (csrc/t4_internal.h)
+        "t4_batch_read": (I, [P, P, P, P, P, P]), "t4_text_lines": (I, [P, P, L, C.POINTER(L)]), "t4_text_tile_bytes": (I, []),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name) and os.environ.get("T4_LIB"):   # an older build of the library under T4_LIB (A/B timing of a kernel): the calls it lacks fail when made
@@ -280,8 +285,11 @@ class Engine:
     def kmer_counter(self, k=21, max_kmers=1 << 20, per_barcode=False):
         return KmerCounter(self, k, max_kmers, per_barcode)
 
-    def upload(self, reads, barcodes=None):
-        return Batch(self, reads, barcodes)
+    def upload(self, reads, barcodes=None, flags=0):
+        return Batch(self, reads, barcodes, flags)
+
+    def text(self, max_piece_bytes=16 << 20):
+        return Text(self, max_piece_bytes)
 
     def close(self):
         if getattr(self, "h", None):
@@ -673,6 +681,12 @@ class Index:
         self.eng.check(self.eng.lib.t4_has_hit(self.h, batch.h, mode, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def candidate_test(self, reads, mates=None):
+        """t4_candidate_test: the stage-0 extractor's keep decision per read (pair) -> uint8 [n]"""
+        keep = np.zeros(reads.n, dtype=np.uint8)
+        self.eng.check(self.eng.lib.t4_candidate_test(self.h, reads.h, None if mates is None else mates.h, keep.ctypes.data_as(C.c_void_p)))
+        return keep
+
     def annotate_rough(self, batch, fetch=True):
         out = np.zeros((batch.n, 4), dtype=OV_DTYPE) if fetch else None
         self.eng.check(self.eng.lib.t4_annotate_rough(self.h, batch.h, out.ctypes.data_as(C.c_void_p) if fetch else None))
@@ -694,7 +708,7 @@ class Batch:
     """t4_batch: 2-bit packed reads in HBM. `reads`: list of str/bytes, or a uint8 [n, stride] array of
     NUL-terminated fixed-stride records (as produced by the synthetic generator)."""
 
-    def __init__(self, eng, reads, barcodes=None):
+    def __init__(self, eng, reads, barcodes=None, flags=0):
         self.eng = eng
         if isinstance(reads, np.ndarray):
             arr = np.ascontiguousarray(reads, dtype=np.uint8)
@@ -724,12 +738,80 @@ class Batch:
             barcodes = np.ascontiguousarray(barcodes, dtype=np.int32)
             bc = barcodes.ctypes.data_as(C.c_void_p)
         h = C.c_void_p()
-        eng.check(eng.lib.t4_reads_upload(eng.h, buf.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), bc, n, C.byref(h)))
+        eng.check(eng.lib.t4_reads_upload_flags(eng.h, buf.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), bc, n, flags, C.byref(h)))
         self.h = h
+
+    @classmethod
+    def from_handle(cls, eng, h, n):
+        """a batch the library made (t4_text_batch)"""
+        b = cls.__new__(cls)
+        b.eng, b.h, b.n = eng, h, n
+        return b
+
+    def read(self):
+        """t4_batch_read (test aid) -> (pk uint32 [n, wpk], nm uint32 [n, wnm], len int32 [n], low uint8 [n], longest read)"""
+        V = C.c_void_p
+        dims = np.zeros(3, dtype=np.int32)
+        self.eng.check(self.eng.lib.t4_batch_read(self.h, dims.ctypes.data_as(V), None, None, None, None))
+        pk, nm = np.zeros((self.n, int(dims[0])), dtype=np.uint32), np.zeros((self.n, int(dims[1])), dtype=np.uint32)
+        ln, low = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.uint8)
+        self.eng.check(self.eng.lib.t4_batch_read(self.h, dims.ctypes.data_as(V), pk.ctypes.data_as(V), nm.ctypes.data_as(V), ln.ctypes.data_as(V), low.ctypes.data_as(V)))
+        return pk, nm, ln, low, int(dims[2])
 
     def close(self):
         if getattr(self, "h", None):
             self.eng.lib.t4_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Text:
+    """t4_text: FASTQ text on the device, piece by piece -- line table, validated records, batches."""
+
+    def __init__(self, eng, max_piece_bytes=16 << 20):
+        self.eng = eng
+        self.h = C.c_void_p()
+        self.nrec = 0
+        eng.check(eng.lib.t4_text_create(eng.h, C.c_int64(max_piece_bytes), C.byref(self.h)))
+
+    def scan(self, data, final=True):
+        """-> (whole records, bytes they take, status, first offending record or -1, longest read)"""
+        data = bytes(data)
+        info = np.zeros(5, dtype=np.int64)
+        self.nrec = 0
+        self.eng.check(self.eng.lib.t4_text_scan(self.h, C.cast(C.c_char_p(data), C.c_void_p), len(data), 1 if final else 0, info.ctypes.data_as(C.c_void_p)))
+        self.nrec = int(info[0])
+        return tuple(int(x) for x in info)
+
+    def batch(self, first=0, n=None):
+        n = self.nrec - first if n is None else n
+        h = C.c_void_p()
+        self.eng.check(self.eng.lib.t4_text_batch(self.h, first, n, C.byref(h)))
+        return Batch.from_handle(self.eng, h, n)
+
+    def records(self, first=0, n=None):
+        """-> (rec_start uint32 [n + 1], low_complexity uint8 [n])"""
+        n = self.nrec - first if n is None else n
+        start, low = np.zeros(n + 1, dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint8)
+        self.eng.check(self.eng.lib.t4_text_records(self.h, first, n, start.ctypes.data_as(C.c_void_p), low.ctypes.data_as(C.c_void_p)))
+        return start, low[:n]
+
+    def lines(self):
+        """t4_text_lines (test aid) -> the line table of the piece last scanned: uint32 [lines + 1] (empty piece: [0])"""
+        n = C.c_int64(0)
+        self.eng.check(self.eng.lib.t4_text_lines(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value + 1, dtype=np.uint32)
+        self.eng.check(self.eng.lib.t4_text_lines(self.h, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.eng.lib.t4_text_destroy(self.h)
             self.h = None
 
     def __del__(self):

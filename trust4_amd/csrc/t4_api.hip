@@ -30,6 +30,7 @@
 #endif
 #include "../../include/trust4_hip.h"
 #include "t4_kernels.h"
+#include "t4_text.h"
 #include "t4_internal.h"
 
 static_assert(sizeof(t4_overlap) == sizeof(T4OverlapOut), "overlap layout");
@@ -331,7 +332,26 @@ struct t4_batch {
   int wpk = 0, wnm = 0, maxLen = 0;
   DevBuf<unsigned> dPk, dNm;
   DevBuf<int> dLen, dBarcode;
+  DevBuf<unsigned char> dLow;   // low-complexity bytes (batches of t4_text_batch; null otherwise: no read counts as low)
   T4BatchView view;
+};
+
+// FASTQ text on the device (t4_text.h): everything one piece needs, allocated once for pieces of up to `cap` bytes.
+struct t4_text {
+  t4_ctx *ctx = nullptr;
+  int64_t cap = 0;
+  PinnedBuf<char> stage;                      // the piece on its way to the device
+  PinnedBuf<unsigned long long> infoHost;     // T4_TEXT_INFO_WORDS words to and from dInfo
+  DevBuf<char> dText;                         // whole tiles
+  DevBuf<unsigned> dTileCnt, dLineStart;      // per tile; per line + 1
+  DevBuf<int> dLen;                           // per record of the piece (at most cap / 4) ...
+  DevBuf<unsigned> dRecStart;
+  DevBuf<unsigned char> dLow;
+  DevBuf<unsigned long long> dInfo;
+  // the piece last scanned
+  int status = -1;                            // -1: none
+  int64_t nbytes = 0, lines = 0, nrec = 0, recBytes = 0, badRec = -1;
+  int longest = 0;
 };
 
 static int fail(t4_ctx *c, int code, const char *fmt, ...) {
@@ -1575,6 +1595,185 @@ int t4_has_hit(t4_index *ref, t4_batch *b, int mode, int32_t *out) {
     HIPCHK(c, hipMemcpyAsync(out, c->counts, sizeof(int) * (size_t)b->n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  return T4_OK;
+}
+
+// ---- FASTQ text on the device (t4_text.h) ---------------------------------------------------------------------------------------
+int t4_text_create(t4_ctx *c, int64_t max_piece_bytes, t4_text **out) {
+  if (!c || !out) return T4_ERR_ARG;
+  *out = nullptr;
+  // (offsets into a piece are 32-bit words, and nbytes + 1 is one of them)
+  if (max_piece_bytes < 1 || max_piece_bytes > ((int64_t)1 << 31)) return fail(c, T4_ERR_ARG, "t4_text_create: a piece has 1 to 2^31 bytes, not %lld", (long long)max_piece_bytes);
+  (void)hipSetDevice(c->device);
+  std::unique_ptr<t4_text> tx(new t4_text());   // (and its buffers, on every way out but the last)
+  tx->ctx = c; tx->cap = max_piece_bytes;
+  const size_t tiles = (size_t)((max_piece_bytes + T4_TEXT_TILE - 1) / T4_TEXT_TILE), recs = (size_t)(max_piece_bytes / 4) + 1;
+  int r;
+  if ((r = tx->stage.alloc(c, (size_t)max_piece_bytes, hipHostMallocDefault)) || (r = tx->infoHost.alloc(c, T4_TEXT_INFO_WORDS, hipHostMallocDefault)) ||
+      (r = tx->dText.alloc(c, tiles * T4_TEXT_TILE)) || (r = tx->dTileCnt.alloc(c, tiles)) || (r = tx->dLineStart.alloc(c, (size_t)max_piece_bytes + 2)) ||
+      (r = tx->dLen.alloc(c, recs)) || (r = tx->dRecStart.alloc(c, recs)) || (r = tx->dLow.alloc(c, recs)) || (r = tx->dInfo.alloc(c, T4_TEXT_INFO_WORDS)))
+    return r;
+  *out = tx.release();
+  return T4_OK;
+}
+
+void t4_text_destroy(t4_text *tx) { delete tx; }
+
+int t4_text_scan(t4_text *tx, const char *text, int64_t nbytes, int final_piece, int64_t info[5]) {
+  if (!tx || !info) return T4_ERR_ARG;
+  t4_ctx *c = tx->ctx;
+  tx->status = -1; tx->nbytes = tx->lines = tx->nrec = tx->recBytes = 0; tx->badRec = -1; tx->longest = 0;
+  if (nbytes < 0 || nbytes > tx->cap || (nbytes > 0 && !text)) return fail(c, T4_ERR_ARG, "t4_text_scan: %lld bytes for a handle made for %lld", (long long)nbytes, (long long)tx->cap);
+  (void)hipSetDevice(c->device);
+  unsigned long long *h = tx->infoHost;
+  h[T4_TEXT_NEWLINES] = 0; h[T4_TEXT_BAD] = ~0ull; h[T4_TEXT_LONGEST] = 0; h[T4_TEXT_END] = 0;
+  int64_t lines = 0, nrec = 0;
+  if (nbytes > 0) {
+    const int tiles = (int)((nbytes + T4_TEXT_TILE - 1) / T4_TEXT_TILE);
+    const int openEnd = final_piece && text[nbytes - 1] != '\n';
+    memcpy(tx->stage, text, (size_t)nbytes);
+    HIPCHK(c, hipMemcpyAsync(tx->dText, tx->stage, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tx->dInfo, h, sizeof(unsigned long long) * T4_TEXT_INFO_WORDS, hipMemcpyHostToDevice, c->stream));
+    launch(t4k::textCountKernel, tiles, T4_TEXT_THREADS, c->stream, tx->dText, (long long)nbytes, tx->dTileCnt);
+    launch(t4k::textScanKernel, 1, T4_TEXT_THREADS, c->stream, tx->dTileCnt, tiles, tx->dInfo);
+    launch(t4k::textFillKernel, tiles, T4_TEXT_THREADS, c->stream, tx->dText, (long long)nbytes, tx->dTileCnt, tx->dLineStart, openEnd, tx->dInfo);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h, tx->dInfo, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    lines = (int64_t)h[T4_TEXT_NEWLINES] + openEnd;
+    nrec = lines / 4;
+    if (nrec > 0) {
+      launch(t4k::textRecordKernel<false>, (int)((nrec * 32 + T4_TEXT_THREADS - 1) / T4_TEXT_THREADS), T4_TEXT_THREADS, c->stream, tx->dText, tx->dLineStart,
+             0ll, (long long)nrec, tx->dLen, tx->dLow, tx->dRecStart, tx->dInfo, nullptr, nullptr, 0, 0);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(h, tx->dInfo, sizeof(unsigned long long) * T4_TEXT_INFO_WORDS, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+  }
+  tx->nbytes = nbytes; tx->lines = lines; tx->nrec = nrec;
+  tx->recBytes = nrec ? std::min<int64_t>((int64_t)h[T4_TEXT_END], nbytes) : 0;   // (a last line without '\n' ends at nbytes)
+  tx->status = 0;
+  if (h[T4_TEXT_BAD] != ~0ull) { tx->status = (int)(h[T4_TEXT_BAD] & 15); tx->badRec = (int64_t)(h[T4_TEXT_BAD] >> 4); }
+  else if (final_piece && lines % 4) { tx->status = 8; tx->badRec = nrec; }
+  tx->longest = (int)h[T4_TEXT_LONGEST];
+  info[0] = nrec; info[1] = tx->recBytes; info[2] = tx->status; info[3] = tx->badRec; info[4] = tx->longest;
+  return T4_OK;
+}
+
+int t4_text_batch(t4_text *tx, int64_t first, int64_t n, t4_batch **out) {
+  if (!tx || !out) return T4_ERR_ARG;
+  *out = nullptr;
+  t4_ctx *c = tx->ctx;
+  if (tx->status < 0) return fail(c, T4_ERR_ARG, "t4_text_batch: no piece has been scanned");
+  if (tx->status > 0) return fail(c, T4_ERR_ARG, "t4_text_batch: the piece has status %d at record %lld", tx->status, (long long)tx->badRec);
+  if (first < 0 || n < 0 || first + n > tx->nrec) return fail(c, T4_ERR_ARG, "t4_text_batch: records [%lld, %lld) of a piece of %lld", (long long)first, (long long)(first + n), (long long)tx->nrec);
+  (void)hipSetDevice(c->device);
+  const int grid = (int)((n + T4_TEXT_THREADS - 1) / T4_TEXT_THREADS);
+  int maxLen = tx->longest;
+  if (n == 0) maxLen = 0;
+  else if (n < tx->nrec) {   // a part of the piece: its own longest read, as the host packer would size the rows
+    unsigned long long *h = tx->infoHost;
+    HIPCHK(c, hipMemsetAsync(tx->dInfo + T4_TEXT_END, 0, sizeof(unsigned long long), c->stream));
+    launch(t4k::textMaxLenKernel, grid, T4_TEXT_THREADS, c->stream, tx->dLen + first, (long long)n, tx->dInfo + T4_TEXT_END);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h, tx->dInfo + T4_TEXT_END, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    maxLen = (int)h[0];
+  }
+  std::unique_ptr<t4_batch> b(new t4_batch());
+  b->ctx = c; b->n = n; b->maxLen = maxLen;
+  b->wpk = std::max(1, (maxLen + 15) / 16); b->wnm = std::max(1, (maxLen + 31) / 32);
+  int r;
+  if ((r = b->dPk.alloc(c, (size_t)n * b->wpk + 4)) || (r = b->dNm.alloc(c, (size_t)n * b->wnm + 4)) || (r = b->dLen.alloc(c, (size_t)n)) || (r = b->dLow.alloc(c, (size_t)n))) return r;
+  if (n > 0) {
+    launch(t4k::textRecordKernel<true>, (int)((n * 32 + T4_TEXT_THREADS - 1) / T4_TEXT_THREADS), T4_TEXT_THREADS, c->stream, tx->dText, tx->dLineStart,
+           (long long)first, (long long)n, b->dLen, b->dLow, nullptr, nullptr, b->dPk, b->dNm, b->wpk, b->wnm);
+    HIPCHK(c, hipGetLastError());
+  }
+  b->view.pk = b->dPk; b->view.nm = b->dNm; b->view.len = b->dLen; b->view.barcode = nullptr;
+  b->view.wpk = b->wpk; b->view.wnm = b->wnm; b->view.n = n;
+  *out = b.release();
+  return T4_OK;
+}
+
+int t4_text_records(t4_text *tx, int64_t first, int64_t n, uint32_t *rec_start, uint8_t *low_complexity) {
+  if (!tx) return T4_ERR_ARG;
+  t4_ctx *c = tx->ctx;
+  if (tx->status < 0) return fail(c, T4_ERR_ARG, "t4_text_records: no piece has been scanned");
+  if (first < 0 || n < 0 || first + n > tx->nrec) return fail(c, T4_ERR_ARG, "t4_text_records: records [%lld, %lld) of a piece of %lld", (long long)first, (long long)(first + n), (long long)tx->nrec);
+  (void)hipSetDevice(c->device);
+  if (rec_start) {
+    const int64_t have = std::min<int64_t>(n + 1, tx->nrec - first);   // (record nrec has no entry: it begins where the whole records end)
+    if (have > 0) HIPCHK(c, hipMemcpyAsync(rec_start, tx->dRecStart + first, sizeof(uint32_t) * (size_t)have, hipMemcpyDeviceToHost, c->stream));
+    if (have < n + 1) rec_start[n] = (uint32_t)tx->recBytes;
+  }
+  if (low_complexity && n > 0) HIPCHK(c, hipMemcpyAsync(low_complexity, tx->dLow + first, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return T4_OK;
+}
+
+// (tests) the line table of the piece last scanned: lines + 1 offsets
+int t4_text_lines(t4_text *tx, uint32_t *line_start, int64_t cap, int64_t *lines) {
+  if (!tx || !lines || tx->status < 0) return T4_ERR_ARG;
+  t4_ctx *c = tx->ctx;
+  *lines = tx->lines;
+  if (!line_start || tx->nbytes == 0) return T4_OK;   // (an empty piece has no table)
+  if (cap < tx->lines + 1) return fail(c, T4_ERR_ARG, "t4_text_lines: room for %lld offsets, the piece has %lld", (long long)cap, (long long)tx->lines + 1);
+  HIPCHK(c, hipMemcpy(line_start, tx->dLineStart, sizeof(uint32_t) * (size_t)(tx->lines + 1), hipMemcpyDeviceToHost));
+  return T4_OK;
+}
+int t4_text_tile_bytes(void) { return T4_TEXT_TILE; }
+
+// (tests) the rows of a batch: dims = words per pk row, words per nm row, longest read; low: zeros for a batch without such bytes
+int t4_batch_read(t4_batch *b, int32_t dims[3], uint32_t *pk, uint32_t *nm, int32_t *len, uint8_t *low) {
+  if (!b) return T4_ERR_ARG;
+  t4_ctx *c = b->ctx;
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (dims) { dims[0] = b->wpk; dims[1] = b->wnm; dims[2] = b->maxLen; }
+  const size_t n = (size_t)b->n;
+  if (n == 0) return T4_OK;
+  if (pk) HIPCHK(c, hipMemcpy(pk, b->dPk, sizeof(uint32_t) * n * b->wpk, hipMemcpyDeviceToHost));
+  if (nm) HIPCHK(c, hipMemcpy(nm, b->dNm, sizeof(uint32_t) * n * b->wnm, hipMemcpyDeviceToHost));
+  if (len) HIPCHK(c, hipMemcpy(len, b->dLen, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  if (low) { if (b->dLow.p) HIPCHK(c, hipMemcpy(low, b->dLow, n, hipMemcpyDeviceToHost)); else memset(low, 0, n); }
+  return T4_OK;
+}
+
+int t4_candidate_test(t4_index *ref, t4_batch *reads, t4_batch *mates, uint8_t *keep) {
+  if (!ref || !reads || !keep) return T4_ERR_ARG;
+  t4_ctx *c = ref->ctx;
+  if (mates && mates->n != reads->n) return fail(c, T4_ERR_ARG, "t4_candidate_test: %lld reads and %lld mates", reads->n, mates->n);
+  if (reads->ctx != c || (mates && mates->ctx != c)) return fail(c, T4_ERR_ARG, "batch belongs to another ctx");
+  const long long n = reads->n;
+  if (n == 0) return T4_OK;
+  (void)hipSetDevice(c->device);
+  DevBuf<int> qlen;
+  DevBuf<unsigned char> pass1, pass;
+  int r;
+  if ((r = qlen.alloc(c, (size_t)n)) || (r = pass1.alloc(c, (size_t)n)) || (mates && (r = pass.alloc(c, (size_t)n)))) return r;
+  const int grid = (int)((n + T4_TEXT_THREADS - 1) / T4_TEXT_THREADS);
+  // one side: the rows that are still to be tested keep their length, the others are queried as empty reads (HasHitInSet = 0)
+  auto side = [&](t4_batch *b, const unsigned char *done, unsigned char *out) -> int {
+    int rr;
+    if ((rr = ensurePerCall(c, n))) return rr;
+    launch(t4k::candLenKernel, grid, T4_TEXT_THREADS, c->stream, b->dLen, b->dLow, done, qlen, n);
+    HIPCHK(c, hipGetLastError());
+    T4QueryArgs qa;
+    memset(&qa, 0, sizeof qa);
+    qa.mode = 5; qa.ret = c->counts;
+    b->view.len = qlen;
+    rr = runQuery(ref, b, qa, false);
+    b->view.len = b->dLen;
+    if (rr) return rr;
+    launch(t4k::candCombineKernel, grid, T4_TEXT_THREADS, c->stream, qlen, c->counts, done, out, n);
+    HIPCHK(c, hipGetLastError());
+    return T4_OK;
+  };
+  if ((r = side(reads, nullptr, pass1))) return r;
+  if (mates && (r = side(mates, pass1, pass))) return r;
+  HIPCHK(c, hipMemcpyAsync(keep, mates ? pass.p : pass1.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return T4_OK;
 }
 

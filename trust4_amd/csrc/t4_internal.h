@@ -105,6 +105,13 @@ int64_t t4_cellset_live_keys_staged(const t4_cellset *cs);
 // the host. *bytes receives the image's size; buf may be null to ask for it.
 int t4_cellstore_read_image(t4_cellstore *cs, int slot, void *buf, size_t cap, size_t *bytes, void *view);
 
+// Test aids of the text front end (t4_text.h): the rows of a batch as they lie on the device (dims: words per pk row, words per nm
+// row, longest read; low: zeros for a batch that carries no low-complexity bytes; any pointer may be null), the line table of the
+// piece last scanned (lines + 1 offsets; *lines alone when line_start is null) and the tile of the line-table kernels.
+int t4_batch_read(t4_batch *b, int32_t dims[3], uint32_t *pk, uint32_t *nm, int32_t *len, uint8_t *low);
+int t4_text_lines(t4_text *tx, uint32_t *line_start, int64_t cap, int64_t *lines);
+int t4_text_tile_bytes(void);
+
 // t4_add_query with variable-size results (a read may overlap thousands of contigs that share a gene segment): counts[i]
 // records of read i start at index base[i] of ov / ext / ext_ret, which point into pinned memory of the ctx that stays
 // valid until the next query on it. tier_hint (nullable, n bytes, in/out): nonzero = the read outgrew the LDS tiers the last

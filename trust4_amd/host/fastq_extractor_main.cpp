@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <chrono>
 #include <condition_variable>
@@ -75,6 +76,74 @@ struct ChunkStream {
     q.pop_front();
     cv.notify_all();
     return true;
+  }
+  void finish() {
+    if (!th.joinable()) return;
+    { std::lock_guard<std::mutex> lk(m); stop = true; }
+    cv.notify_all();
+    th.join();
+  }
+};
+
+// The raw bytes of one input file (inflated when it is gzip: gzread yields the same bytes) read ahead on a thread of its own in
+// chunks, for the device path (T4_GPU_PARSE=1): the main thread takes them into its current piece while the last one is on the device.
+struct ByteStream {
+  static constexpr size_t DEPTH = 4;
+  std::string path;
+  size_t chunkBytes = 0;
+  std::thread th;
+  std::mutex m;
+  std::condition_variable cv;
+  std::deque<std::vector<char>> q;
+  size_t at = 0;   // bytes of q.front() already taken
+  bool done = false, stop = false, failed = false;
+  void start(const std::string &file, size_t chunk) {
+    path = file; chunkBytes = chunk ? chunk : 1;
+    th = std::thread([this]() {
+      FILE *raw = nullptr;
+      gzFile gz = nullptr;
+      struct stat st;
+      if (stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (raw = fopen(path.c_str(), "rb"))) {   // (as SeqReader::openNext tells the two apart)
+        unsigned char magic[2] = {0, 0};
+        const size_t got = fread(magic, 1, 2, raw);
+        if ((got == 2 && magic[0] == 0x1f && magic[1] == 0x8b) || fseek(raw, 0, SEEK_SET) != 0) { fclose(raw); raw = nullptr; }
+      }
+      if (!raw && (gz = gzopen(path.c_str(), "rb"))) gzbuffer(gz, 1 << 20);
+      bool bad = !raw && !gz;
+      for (; !bad;) {
+        std::vector<char> v(chunkBytes);
+        size_t got = 0;
+        if (raw) got = fread(v.data(), 1, v.size(), raw);
+        else { const int r = gzread(gz, v.data(), (unsigned)v.size()); if (r < 0) { bad = true; break; } got = (size_t)r; }
+        v.resize(got);
+        std::unique_lock<std::mutex> lk(m);
+        if (got) q.push_back(std::move(v));
+        if (got < chunkBytes) break;
+        cv.notify_all();
+        cv.wait(lk, [this]() { return q.size() < DEPTH || stop; });
+        if (stop) break;
+      }
+      if (raw) fclose(raw);
+      if (gz) gzclose(gz);
+      std::lock_guard<std::mutex> lk(m);
+      failed = bad; done = true;
+      cv.notify_all();
+    });
+  }
+  // up to `want` bytes to dst; fewer only at the end of the file. *ended: nothing is left behind them.
+  size_t take(char *dst, size_t want, bool *ended) {
+    size_t got = 0;
+    std::unique_lock<std::mutex> lk(m);
+    for (;;) {
+      cv.wait(lk, [this]() { return !q.empty() || done; });
+      if (q.empty()) { *ended = true; return got; }
+      if (got == want) { *ended = false; return got; }
+      std::vector<char> &f = q.front();
+      const size_t k = std::min(want - got, f.size() - at);
+      memcpy(dst + got, f.data() + at, k);
+      got += k; at += k;
+      if (at == f.size()) { q.pop_front(); at = 0; cv.notify_all(); }
+    }
   }
   void finish() {
     if (!th.joinable()) return;
@@ -220,6 +289,127 @@ int main(int argc, char *argv[]) {
   const size_t BATCH = getenv("T4_BATCH") ? (size_t)atol(getenv("T4_BATCH")) : (size_t)1 << 18;
   std::vector<Rec> r1, r2, rb, ru;
   long long total = 0, kept = 0;
+  auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+
+  // ---- the device path (T4_GPU_PARSE=1): the files' bytes go to the device piece by piece, which finds the records, validates and
+  // packs them and runs the candidate test (t4_text_*, t4_candidate_test); the host touches the text of the kept records only.
+  // It takes text for which "four lines per record" and SeqReader mean the same; at the first piece that is anything else the whole
+  // input is run on the host path below.
+  const char *hostWhy = nullptr;
+  if (!(getenv("T4_GPU_PARSE") && atoi(getenv("T4_GPU_PARSE")) == 1)) hostWhy = "T4_GPU_PARSE is not 1";
+  else if (hasBarcode) hostWhy = "--barcode";
+  else if (hasUmi) hostWhy = "--UMI";
+  else if (reads.files.size() != 1 || (hasMate && mateReads.files.size() != 1)) hostWhy = "more than one file per mate";
+  for (int cat = 0; cat < FMT_COUNT && !hostWhy; ++cat) if (!fmt.segs[cat].empty()) hostWhy = "--readFormat or a range option";
+  if (!hostWhy) {
+    size_t pieceBytes = (size_t)16 << 20;
+#ifdef T4_TEST_KNOBS
+    if (getenv("T4_TEST_TEXT_PIECE")) pieceBytes = (size_t)atol(getenv("T4_TEST_TEXT_PIECE"));   // test builds: small inputs cross piece boundaries
+#endif
+    gpuReady();
+    const int nSide = hasMate ? 2 : 1;
+    struct Side {
+      ByteStream in;
+      t4_text *tx = nullptr;
+      std::vector<char> buf;
+      size_t fill = 0;          // bytes of buf in use: what the last piece left over, then fresh bytes
+      bool ended = false;       // the file has no bytes beyond buf[fill)
+      long long recBase = 0;    // records of the file ahead of this piece
+      int64_t info[5] = {0, 0, 0, -1, 0};
+      std::vector<uint32_t> recStart;
+    } side[2];
+    for (int s = 0; s < nSide; ++s) {
+      if ((rc = t4_text_create(ctx, (int64_t)pieceBytes, &side[s].tx))) die(ctx, "t4_text_create", rc);
+      side[s].buf.resize(pieceBytes);
+      side[s].in.start(s == 0 ? reads.files[0] : mateReads.files[0], std::max<size_t>(1, std::min<size_t>(pieceBytes / 4, (size_t)4 << 20)));
+    }
+    auto closeText = [&]() { for (int s = 0; s < nSide; ++s) { side[s].in.finish(); t4_text_destroy(side[s].tx); side[s].tx = nullptr; } };
+    double secWait = 0, secDevice = 0, secWrite = 0;
+    int fallStatus = 0; long long fallRec = -1; int fallSide = 0;
+    std::vector<uint8_t> keep;
+    Rec o1, o2;
+    o1.hasQual = o2.hasQual = true;
+    // record k of the piece: its id (mate 1 only), sequence and qualities cut out of the text
+    auto cut = [&](const Side &sd, size_t k, Rec &r, bool wantId) {
+      const char *p = sd.buf.data() + sd.recStart[k], *end = sd.buf.data() + sd.recStart[k + 1];
+      const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
+      if (wantId) splitHeader(p, (size_t)(nl - p), reads.stripMateSuffix, r.id, nullptr);
+      const char *sq = nl + 1, *sqEnd = (const char *)memchr(sq, '\n', (size_t)(end - sq));
+      r.seq.assign(sq, (size_t)(sqEnd - sq));
+      const char *ql = (const char *)memchr(sqEnd + 1, '\n', (size_t)(end - sqEnd - 1)) + 1;
+      r.qual.assign(ql, r.seq.size());   // (validated: as long as the sequence)
+    };
+    for (;;) {
+      double t0 = now();
+      for (int s = 0; s < nSide; ++s) {
+        Side &sd = side[s];
+        if (!sd.ended) sd.fill += sd.in.take(sd.buf.data() + sd.fill, pieceBytes - sd.fill, &sd.ended);
+        if (sd.in.failed) { closeText(); fprintf(stderr, "Could not open %s\n", sd.in.path.c_str()); exit(EXIT_FAILURE); }
+      }
+      secWait += now() - t0; t0 = now();
+      for (int s = 0; s < nSide && !fallStatus; ++s) {
+        Side &sd = side[s];
+        if ((rc = t4_text_scan(sd.tx, sd.buf.data(), (int64_t)sd.fill, sd.ended ? 1 : 0, sd.info))) die(ctx, "t4_text_scan", rc);
+        if (sd.info[2]) { fallStatus = (int)sd.info[2]; fallRec = sd.recBase + sd.info[3]; fallSide = s; }
+      }
+      if (fallStatus) break;
+      const int64_t n1 = side[0].info[0], n2 = hasMate ? side[1].info[0] : n1, m = std::min(n1, n2);
+      if (m == 0) {
+        if (n1 == 0 && side[0].ended) break;   // every read has been seen (what the mate file has beyond them is not looked at, as on the host path)
+        if (hasMate && n2 == 0 && side[1].ended) {
+          closeText();
+          fprintf(stderr, "The two mate-pair read files have different number of reads.\n");
+          exit(1);
+        }
+        fallStatus = 9; fallSide = n1 == 0 ? 0 : 1; fallRec = side[fallSide].recBase;   // a record that does not fit a piece
+        break;
+      }
+      t4_batch *b1 = nullptr, *b2 = nullptr;
+      keep.resize((size_t)m);
+      for (int s = 0; s < nSide; ++s) {
+        side[s].recStart.resize((size_t)m + 1);
+        if ((rc = t4_text_batch(side[s].tx, 0, m, s == 0 ? &b1 : &b2))) die(ctx, "t4_text_batch", rc);
+        if ((rc = t4_text_records(side[s].tx, 0, m, side[s].recStart.data(), nullptr))) die(ctx, "t4_text_records", rc);
+      }
+      if ((rc = t4_candidate_test(refSet, b1, b2, keep.data()))) die(ctx, "t4_candidate_test", rc);
+      t4_batch_destroy(b1);
+      t4_batch_destroy(b2);
+      secDevice += now() - t0; t0 = now();
+      for (size_t k = 0; k < (size_t)m; ++k) {
+        if (!keep[k]) continue;
+        cut(side[0], k, o1, true);
+        outputSeq(fp1, o1.id, o1, FMT_READ1);
+        if (hasMate) { cut(side[1], k, o2, false); outputSeq(fp2, o1.id, o2, FMT_READ2); }
+        ++kept;
+      }
+      total += (long long)m;
+      for (int s = 0; s < nSide; ++s) {   // what the piece holds beyond record m goes to the front of the next one
+        Side &sd = side[s];
+        const size_t used = sd.recStart[(size_t)m];
+        memmove(sd.buf.data(), sd.buf.data() + used, sd.fill - used);
+        sd.fill -= used; sd.recBase += m;
+      }
+      secWrite += now() - t0;
+    }
+    closeText();
+    if (!fallStatus) {
+      if (getenv("T4_TIMING")) fprintf(stderr, "path: device text (T4_GPU_PARSE=1, pieces of %zu bytes)\ntiming: %.2f s waiting for pieces, %.2f s on the device, %.2f s writing\n", pieceBytes, secWait, secDevice, secWrite);
+      fclose(fp1);
+      if (fp2) fclose(fp2);
+      fprintf(stderr, "fastq-extractor-hip: %lld of %lld %s kept (hitLenRequired %d)\n", kept, total, hasMate ? "pairs" : "reads", hitLenRequired);
+      t4_index_destroy(refSet);
+      t4_destroy(ctx);
+      return 0;
+    }
+    fprintf(stderr, "fastq-extractor-hip: T4_GPU_PARSE: status %d at record %lld of %s; the whole input goes to the host path\n", fallStatus, fallRec,
+            side[fallSide].in.path.c_str());
+    hostWhy = "the device path gave the input back";
+    fp1 = freopen((prefix + (hasMate ? "_1.fq" : ".fq")).c_str(), "w", fp1);   // (truncates what the device path wrote)
+    if (fp2) fp2 = freopen((prefix + "_2.fq").c_str(), "w", fp2);
+    if (!fp1 || (hasMate && !fp2)) { fprintf(stderr, "Could not open the output files of %s\n", prefix.c_str()); return EXIT_FAILURE; }
+    total = kept = 0;
+  }
+  if (getenv("T4_TIMING")) fprintf(stderr, "path: host (%s)\n", hostWhy);
   auto test = [&](const std::vector<Rec> &rs, const std::vector<char> *already, std::vector<char> &good) {
     // HasHitInSet for the reads that still need it and pass the low-complexity filter
     std::string bases; std::vector<int64_t> off(1, 0); std::vector<int> which;
@@ -268,7 +458,6 @@ int main(int argc, char *argv[]) {
   std::vector<Rec> c1, c2, cb, cu;
   auto append = [](std::vector<Rec> &dst, std::vector<Rec> &src, size_t n) { for (size_t k = 0; k < n; ++k) dst.push_back(std::move(src[k])); src.clear(); };
   double secWait = 0, secFlush = 0;
-  auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double tw = now();
   while (s1.pop(c1)) {
     const size_t n = c1.size();

@@ -13,6 +13,18 @@
 #include <thread>
 #include <vector>
 
+// A header line ('@' or '>' first, n bytes, no line end) as kseq splits it: the name ends at the first blank or tab, the rest is the
+// comment (null: not wanted). stripMateSuffix: a trailing /1 or /2 of the name goes, as ReadFiles.hpp:180-185 (Next()) drops it; the
+// reference's batch reader NextWithBuffer (200-241) does not.
+inline void splitHeader(const char *line, size_t n, bool stripMateSuffix, std::string &id, std::string *comment) {
+  size_t e = 1;
+  while (e < n && line[e] != ' ' && line[e] != '\t') ++e;
+  id.assign(line + 1, e - 1);
+  if (comment) { if (e < n) comment->assign(line + e + 1, n - e - 1); else comment->clear(); }
+  const size_t l = id.size();
+  if (stripMateSuffix && l >= 2 && (id[l - 1] == '1' || id[l - 1] == '2') && id[l - 2] == '/') id.resize(l - 2);
+}
+
 // ---- FASTA / FASTQ (optionally gzip) reader with kseq's record model ---------------------------------
 struct SeqReader {
   std::vector<std::string> files;
@@ -97,12 +109,7 @@ struct SeqReader {
       bool got = false;
       while (getLine(line)) if (!line.empty() && (line[0] == '>' || line[0] == '@')) { got = true; break; }
       if (!got) { closeCur(); ++cur; havePending = false; continue; }
-      size_t e = 1;
-      while (e < line.size() && line[e] != ' ' && line[e] != '\t') ++e;
-      id.assign(line, 1, e - 1);
-      if (e < line.size()) comment.assign(line, e + 1, std::string::npos); else comment.clear();
-      size_t n = id.size();   // ReadFiles.hpp:180-185 (Next() drops a /1 or /2; the batch reader NextWithBuffer, 200-241, does not)
-      if (stripMateSuffix && n >= 2 && (id[n - 1] == '1' || id[n - 1] == '2') && id[n - 2] == '/') id.resize(n - 2);
+      splitHeader(line.data(), line.size(), stripMateSuffix, id, &comment);
       seq.clear(); qual.clear(); hasQual = false;
       bool plus = false;
       while (getLine(line)) {
