@@ -290,6 +290,20 @@ int t4_mate_overlap(t4_ctx *ctx, int n, const int64_t *first_off, const char *fi
 int t4_process_pairs(t4_ctx *ctx, int n, const int64_t *off1, const char *r1, const char *q1, const int64_t *off2, const char *r2,
                      const char *q2, const unsigned char *has_qual, const int64_t *out_off, char *out_r, char *out_q, int32_t *meta4);
 
+/* t4_process_pairs for pairs whose text is on the device already: pair i is record first_read + i of the piece `reads` last
+ * scanned and record first_mate + i of the piece `mates` last scanned (two handles of one ctx, both pieces with status 0; FASTQ
+ * records always have qualities). Nothing is marshalled on the host. skip (n bytes, or NULL): a pair with skip[i] != 0 is not
+ * looked at; its meta4 is {-1, 0, 0, -1}. meta4 receives 4 int32 per pair: kind, length of read 1 afterwards and flags as
+ * t4_process_pairs gives them, and where a changed read 1 (flag 16) stands: its bases begin at out_r + meta4[4 i + 3], its qualities
+ * at out_q + meta4[4 i + 3]; -1 for a pair whose read 1 is the record's own. Changed reads are written back to back in no stated
+ * order; *out_bytes receives the bytes they take. out_cap: room in out_r and in out_q (either may be NULL when it is 0). The
+ * sequence bytes of the n pairs are always enough, and so is half the bytes of the two pieces. With less room than the changed
+ * reads need the call returns T4_ERR_ARG with *out_bytes = the need and meta4 complete but for the fourth words, and may be repeated.
+ * T4_ERR_ARG also for handles of two contexts, an unscanned piece or one with a status other than 0, and a range beyond a piece's
+ * records. The buffers of the call belong to `reads`: made by its first call, reused, freed by t4_text_destroy. */
+int t4_text_process_pairs(t4_text *reads, t4_text *mates, int64_t first_read, int64_t first_mate, int64_t n, const uint8_t *skip,
+                          int32_t *meta4, char *out_r, char *out_q, int64_t out_cap, int64_t *out_bytes);
+
 /* ---- ordered contig builder (host-side commit logic + GPU queries) ----------------------------------
  * t4_assembler owns a mutable set of novel contigs (the reference's `SeqSet seqSet`, main.cpp:642) and exposes
  * the members stage 1 calls on it, with the same arguments and return values:

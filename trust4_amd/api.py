@@ -104,6 +104,7 @@ def _load():
         "t4_add_query_last_long_lists": (I, [P, C.POINTER(P), C.POINTER(I)]),
         # FASTQ text on the device
         "t4_text_create": (I, [P, L, C.POINTER(P)]), "t4_text_destroy": (None, [P]), "t4_text_scan": (I, [P, P, L, I, P]),
+        "t4_text_process_pairs": (I, [P, P, L, L, L, P, P, P, P, L, C.POINTER(L)]),
         "t4_text_batch": (I, [P, L, L, C.POINTER(P)]), "t4_text_records": (I, [P, L, L, P, P]), "t4_candidate_test": (I, [P, P, P, P]),
         # ... and its test aids (csrc/t4_internal.h)
         "t4_batch_read": (I, [P, P, P, P, P, P]), "t4_text_lines": (I, [P, P, L, C.POINTER(L)]), "t4_text_tile_bytes": (I, []),
@@ -777,6 +778,7 @@ class Text:
         self.eng = eng
         self.h = C.c_void_p()
         self.nrec = 0
+        self.data = b""   # the piece last scanned
         eng.check(eng.lib.t4_text_create(eng.h, C.c_int64(max_piece_bytes), C.byref(self.h)))
 
     def scan(self, data, final=True):
@@ -784,6 +786,7 @@ class Text:
         data = bytes(data)
         info = np.zeros(5, dtype=np.int64)
         self.nrec = 0
+        self.data = data
         self.eng.check(self.eng.lib.t4_text_scan(self.h, C.cast(C.c_char_p(data), C.c_void_p), len(data), 1 if final else 0, info.ctypes.data_as(C.c_void_p)))
         self.nrec = int(info[0])
         return tuple(int(x) for x in info)
@@ -800,6 +803,44 @@ class Text:
         start, low = np.zeros(n + 1, dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint8)
         self.eng.check(self.eng.lib.t4_text_records(self.h, first, n, start.ctypes.data_as(C.c_void_p), low.ctypes.data_as(C.c_void_p)))
         return start, low[:n]
+
+    def process_pairs_raw(self, mates, first=0, first_mate=0, n=None, skip=None, out_cap=None):
+        """t4_text_process_pairs -> (meta int32 [n, 4], bases uint8 [out_bytes], qualities uint8 [out_bytes], out_bytes); out_cap None:
+        the sequence bytes of the two pieces at most, which is always enough. A T4Error of too little room carries .out_bytes and .meta"""
+        n = self.nrec - first if n is None else n
+        V = C.c_void_p
+        cap = (len(self.data) + len(mates.data)) // 2 if out_cap is None else out_cap
+        meta = np.zeros((max(n, 1), 4), dtype=np.int32)
+        outr, outq = np.zeros(max(cap, 1), dtype=np.uint8), np.zeros(max(cap, 1), dtype=np.uint8)
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+        used = C.c_int64(0)
+        try:
+            self.eng.check(self.eng.lib.t4_text_process_pairs(self.h, mates.h, first, first_mate, n, None if sk is None else sk.ctypes.data_as(V), meta.ctypes.data_as(V),
+                                                              outr.ctypes.data_as(V), outq.ctypes.data_as(V), cap, C.byref(used)))
+        except T4Error as e:
+            e.out_bytes, e.meta = used.value, meta[:max(n, 0)]
+            raise
+        return meta[:n], outr[:used.value], outq[:used.value], used.value
+
+    def process_pairs(self, mates, first=0, first_mate=0, n=None, skip=None):
+        """ProcessRead of the pairs (record first + i of this piece, record first_mate + i of the piece of `mates`), i < n (default: to
+        the end of this piece) -> what Engine.process_pairs gives for them: a list of (kind, read 1 afterwards, its qualities as bytes,
+        flags); None for a pair whose skip byte is not 0"""
+        meta, outr, outq, _ = self.process_pairs_raw(mates, first, first_mate, n, skip)
+        ls, res = None, []
+        for i in range(len(meta)):
+            kind, ln, fl, at = (int(x) for x in meta[i])
+            if kind < 0:
+                res.append(None)
+                continue
+            if fl & 16:
+                rd = outr[at:at + ln].tobytes().decode("latin-1"); ql = outq[at:at + ln].tobytes()
+            else:
+                ls = self.lines() if ls is None else ls
+                a, b = int(ls[4 * (first + i) + 1]), int(ls[4 * (first + i) + 3])
+                rd = self.data[a:a + ln].decode("latin-1"); ql = self.data[b:b + ln]
+            res.append((kind, rd, ql, fl & 15))
+        return res
 
     def lines(self):
         """t4_text_lines (test aid) -> the line table of the piece last scanned: uint32 [lines + 1] (empty piece: [0])"""

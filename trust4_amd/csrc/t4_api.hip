@@ -348,6 +348,13 @@ struct t4_text {
   DevBuf<unsigned> dRecStart;
   DevBuf<unsigned char> dLow;
   DevBuf<unsigned long long> dInfo;
+  // t4_text_process_pairs with this handle as `reads`: made by the first call, reused
+  DevBuf<int4> dPairMeta;                     // per record of the piece
+  DevBuf<unsigned char> dPairSkip;
+  DevBuf<char> dPairR, dPairQ;                // changed reads and their qualities, pairCap bytes each
+  DevBuf<unsigned long long> dPairNeed;       // bytes the changed reads take
+  PinnedBuf<unsigned long long> pairNeedHost;
+  int64_t pairCap = 0;
   // the piece last scanned
   int status = -1;                            // -1: none
   int64_t nbytes = 0, lines = 0, nrec = 0, recBytes = 0, badRec = -1;
@@ -1709,6 +1716,57 @@ int t4_text_records(t4_text *tx, int64_t first, int64_t n, uint32_t *rec_start, 
   }
   if (low_complexity && n > 0) HIPCHK(c, hipMemcpyAsync(low_complexity, tx->dLow + first, (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return T4_OK;
+}
+
+int t4_text_process_pairs(t4_text *reads, t4_text *mates, int64_t first_read, int64_t first_mate, int64_t n, const uint8_t *skip,
+                          int32_t *meta4, char *out_r, char *out_q, int64_t out_cap, int64_t *out_bytes) {
+  if (!reads || !mates || !out_bytes) return T4_ERR_ARG;
+  t4_ctx *c = reads->ctx;
+  *out_bytes = 0;
+  if (mates->ctx != c) return fail(c, T4_ERR_ARG, "t4_text_process_pairs: the two pieces belong to different contexts");
+  const t4_text *side[2] = {reads, mates};
+  const int64_t firsts[2] = {first_read, first_mate};
+  for (int k = 0; k < 2; ++k) {
+    const char *what = k ? "mates" : "reads";
+    if (side[k]->status < 0) return fail(c, T4_ERR_ARG, "t4_text_process_pairs: no piece of the %s has been scanned", what);
+    if (side[k]->status > 0) return fail(c, T4_ERR_ARG, "t4_text_process_pairs: the piece of the %s has status %d at record %lld", what, side[k]->status, (long long)side[k]->badRec);
+    if (firsts[k] < 0 || n < 0 || firsts[k] + n > side[k]->nrec)
+      return fail(c, T4_ERR_ARG, "t4_text_process_pairs: records [%lld, %lld) of a piece of the %s of %lld", (long long)firsts[k], (long long)(firsts[k] + n), what, (long long)side[k]->nrec);
+  }
+  if (out_cap < 0 || (n > 0 && !meta4) || (out_cap > 0 && (!out_r || !out_q))) return fail(c, T4_ERR_ARG, "t4_text_process_pairs: no room for the result");
+  if (n == 0) return T4_OK;
+  (void)hipSetDevice(c->device);
+  t4_text *tx = reads;
+  int r;
+  const size_t recs = (size_t)(tx->cap / 4) + 1;
+  if ((!tx->dPairMeta.p && (r = tx->dPairMeta.alloc(c, recs))) || (!tx->dPairSkip.p && (r = tx->dPairSkip.alloc(c, recs))) ||
+      (!tx->dPairNeed.p && (r = tx->dPairNeed.alloc(c, 1))) || (!tx->pairNeedHost.p && (r = tx->pairNeedHost.alloc(c, 1, hipHostMallocDefault)))) return r;
+  // room on the device: what the caller has, but never more than the changed reads of these two pieces can take (a record spends at
+  // least twice its read's length, and offsets are 32-bit words)
+  const int64_t room = std::min<int64_t>(std::min<int64_t>(out_cap, (reads->nbytes + mates->nbytes) / 2), 0x7fffffff);
+  if (room > tx->pairCap) {
+    tx->pairCap = 0;
+    if ((r = tx->dPairR.alloc(c, (size_t)room)) || (r = tx->dPairQ.alloc(c, (size_t)room))) return r;
+    tx->pairCap = room;
+  }
+  if (skip) HIPCHK(c, hipMemcpyAsync(tx->dPairSkip, skip, (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(tx->dPairNeed, 0, sizeof(unsigned long long), c->stream));
+  const int grid = (int)std::min<int64_t>(n, (int64_t)c->cus * 32);
+  launch(t4k::textProcessPairKernel, grid, 64, c->stream, reads->dText, reads->dLineStart, (long long)first_read, mates->dText, mates->dLineStart,
+         (long long)first_mate, (long long)n, skip ? tx->dPairSkip.p : nullptr, tx->dPairR, tx->dPairQ, (long long)room, tx->dPairNeed, tx->dPairMeta);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(tx->pairNeedHost, tx->dPairNeed, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(meta4, tx->dPairMeta, sizeof(int4) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int64_t need = (int64_t)tx->pairNeedHost[0];
+  *out_bytes = need;
+  if (need > room) return fail(c, T4_ERR_ARG, "t4_text_process_pairs: the changed reads take %lld bytes, there is room for %lld", (long long)need, (long long)out_cap);
+  if (need > 0) {
+    HIPCHK(c, hipMemcpyAsync(out_r, tx->dPairR, (size_t)need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_q, tx->dPairQ, (size_t)need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
   return T4_OK;
 }
 

@@ -4985,6 +4985,61 @@ __device__ bool lowComplexityWave(const char *s, int n) {
   if (cA >= n / 2 || cC >= n / 2 || cG >= n / 2 || cT >= n / 2 || cN >= n / 10) return true;
   return ((cA <= 2) + (cC <= 2) + (cG <= 2) + (cT <= 2)) >= 2;
 }
+// The pair staged in LDS by one wavefront (s_r1 / s_q1: read 1 and its qualities; s_f / s_fq: the reverse complement of read 2 and its
+// qualities reversed): everything behind the staging. A changed read 1 (flag 16) is left in s_m / s_mq. Every lane gets the same values.
+__device__ __forceinline__ void processPairStaged(const char *s_r1, const char *s_q1, const char *s_f, const char *s_fq, char *s_m, char *s_mq, int slen, int flen,
+                                                  bool hq1, bool hq2, int &kind, int &outLen, int &flags) {
+  const int lane = laneId();
+  int mo = (flen + slen) / 10, mo2 = (flen + slen) / 20;
+  if (mo > 31) mo = 31;
+  if (mo2 > 31) mo2 = 31;
+  int offset, best;
+  kind = 0; outLen = slen; flags = hq1 ? 8 : 0;
+  bool r2Alive = true;
+  const char *fin = s_r1;   // where the final read 1 stands
+  int ov = mateOverlapWave(s_f, flen, s_r1, slen, mo, false, offset, best);
+  if (ov >= 0) {
+    kind = 1; outLen = ov; r2Alive = false; flags |= 16;
+    for (int j = lane; j < ov; j += 64) {
+      char b = s_r1[j], q = s_q1[j];
+      if (hq1 && (s_fq[j + offset] > q || b == 'N')) { b = s_f[j + offset]; q = s_fq[j + offset]; }
+      s_m[j] = b; s_mq[j] = q;
+    }
+    fin = s_m;
+  } else if ((ov = mateOverlapWave(s_r1, slen, s_f, flen, mo2, true, offset, best)) >= 0) {
+    r2Alive = false;
+    if ((double)best >= 0.95 * (double)ov) {
+      kind = 2; flags |= 4 | 16;
+      const int len = offset + flen;
+      for (int j = lane; j < len; j += 64) {
+        char b = j >= offset ? s_f[j - offset] : 0, q = j >= offset ? s_fq[j - offset] : 0;   // qualities of a mate without any read as 0
+        if (j < slen && (j < offset || (int)s_q1[j] >= (int)q - 14 || b == 'N')) { b = s_r1[j]; q = s_q1[j]; }
+        s_m[j] = b; s_mq[j] = q;
+      }
+      outLen = len; fin = s_m;
+    } else {
+      kind = 3;
+      bool useFirst = true;
+      if (hq1) {
+        int a = 0, b = 0;
+        for (int j = offset + lane; j < slen; j += 64) a += (int)s_q1[j] - 32;
+        for (int j = flen - 1 - lane; j >= flen - ov; j -= 64) b += (int)s_fq[j] - 32;
+        a = waveSum(a); b = waveSum(b);
+        double da = (double)a, db = (double)b;
+        da /= ov; db /= ov;
+        if (da + 10 < db) useFirst = false;
+      }
+      if (!useFirst) {   // read 2 as it was read, with the qualities in the order of its reverse complement (as the reference leaves them)
+        flags = (flags & ~8) | (hq2 ? 8 : 0) | 16;
+        for (int j = lane; j < flen; j += 64) { s_m[j] = rcChar(s_f[flen - 1 - j]); s_mq[j] = s_fq[j]; }
+        outLen = flen; fin = s_m;
+      }
+    }
+  }
+  __syncthreads();
+  if (!lowComplexityWave(fin, outLen)) flags |= 1;
+  if (r2Alive && !lowComplexityWave(s_f, flen)) flags |= 2;
+}
 __global__ __launch_bounds__(64) void processPairKernel(int n, const long long *off1, const char *r1, const char *q1, const long long *off2, const char *r2,
                                                       const char *q2, const unsigned char *hasQual, const long long *outOff, char *outR, char *outQ, int4 *meta) {
   __shared__ char s_r1[T4_MAXL + 8], s_q1[T4_MAXL + 8], s_f[T4_MAXL + 8], s_fq[T4_MAXL + 8];
@@ -4997,54 +5052,8 @@ __global__ __launch_bounds__(64) void processPairKernel(int n, const long long *
     for (int i = lane; i < slen; i += 64) { s_r1[i] = r1[off1[p] + i]; s_q1[i] = hq1 ? q1[off1[p] + i] : 0; }
     for (int i = lane; i < flen; i += 64) { s_f[i] = rcChar(r2[off2[p] + flen - 1 - i]); s_fq[i] = hq2 ? q2[off2[p] + flen - 1 - i] : 0; }
     __syncthreads();
-    int mo = (flen + slen) / 10, mo2 = (flen + slen) / 20;
-    if (mo > 31) mo = 31;
-    if (mo2 > 31) mo2 = 31;
-    int kind = 0, outLen = slen, flags = hq1 ? 8 : 0, offset, best;
-    bool r2Alive = true;
-    const char *fin = s_r1;   // where the final read 1 stands
-    int ov = mateOverlapWave(s_f, flen, s_r1, slen, mo, false, offset, best);
-    if (ov >= 0) {
-      kind = 1; outLen = ov; r2Alive = false; flags |= 16;
-      for (int j = lane; j < ov; j += 64) {
-        char b = s_r1[j], q = s_q1[j];
-        if (hq1 && (s_fq[j + offset] > q || b == 'N')) { b = s_f[j + offset]; q = s_fq[j + offset]; }
-        s_m[j] = b; s_mq[j] = q;
-      }
-      fin = s_m;
-    } else if ((ov = mateOverlapWave(s_r1, slen, s_f, flen, mo2, true, offset, best)) >= 0) {
-      r2Alive = false;
-      if ((double)best >= 0.95 * (double)ov) {
-        kind = 2; flags |= 4 | 16;
-        const int len = offset + flen;
-        for (int j = lane; j < len; j += 64) {
-          char b = j >= offset ? s_f[j - offset] : 0, q = j >= offset ? s_fq[j - offset] : 0;   // qualities of a mate without any read as 0
-          if (j < slen && (j < offset || (int)s_q1[j] >= (int)q - 14 || b == 'N')) { b = s_r1[j]; q = s_q1[j]; }
-          s_m[j] = b; s_mq[j] = q;
-        }
-        outLen = len; fin = s_m;
-      } else {
-        kind = 3;
-        bool useFirst = true;
-        if (hq1) {
-          int a = 0, b = 0;
-          for (int j = offset + lane; j < slen; j += 64) a += (int)s_q1[j] - 32;
-          for (int j = flen - 1 - lane; j >= flen - ov; j -= 64) b += (int)s_fq[j] - 32;
-          a = waveSum(a); b = waveSum(b);
-          double da = (double)a, db = (double)b;
-          da /= ov; db /= ov;
-          if (da + 10 < db) useFirst = false;
-        }
-        if (!useFirst) {   // read 2 as it was read, with the qualities in the order of its reverse complement (as the reference leaves them)
-          flags = (flags & ~8) | (hq2 ? 8 : 0) | 16;
-          for (int j = lane; j < flen; j += 64) { s_m[j] = rcChar(s_f[flen - 1 - j]); s_mq[j] = s_fq[j]; }
-          outLen = flen; fin = s_m;
-        }
-      }
-    }
-    __syncthreads();
-    if (!lowComplexityWave(fin, outLen)) flags |= 1;
-    if (r2Alive && !lowComplexityWave(s_f, flen)) flags |= 2;
+    int kind, outLen, flags;
+    processPairStaged(s_r1, s_q1, s_f, s_fq, s_m, s_mq, slen, flen, hq1, hq2, kind, outLen, flags);
     if (flags & 16) for (int j = lane; j < outLen; j += 64) { outR[outOff[p] + j] = s_m[j]; outQ[outOff[p] + j] = s_mq[j]; }
     if (lane == 0) meta[p] = make_int4(kind, outLen, flags, 0);
     __syncthreads();

@@ -1,5 +1,6 @@
-// trust4_amd/csrc/t4_text.h -- FASTQ text on the device: line table, record validation, 2-bit packing, the low-complexity rule and
-// the combine step of the stage-0 candidate test (included by t4_api.hip behind t4_kernels.h, namespace t4k).
+// trust4_amd/csrc/t4_text.h -- FASTQ text on the device: line table, record validation, 2-bit packing, the low-complexity rule, the
+// combine step of the stage-0 candidate test and stage 1's ProcessRead on pairs that lie in two pieces (included by t4_api.hip
+// behind t4_kernels.h, namespace t4k).
 //
 // A piece of text of nbytes bytes lies in device memory padded to a whole number of tiles (T4_TEXT_TILE bytes, one workgroup of
 // T4_TEXT_THREADS lanes with one 16-byte load each), so every load is in bounds; bytes at or beyond nbytes never count. Line j of the
@@ -182,6 +183,47 @@ __global__ __launch_bounds__(T4_TEXT_THREADS) void textMaxLenKernel(const int *l
   int v = i < n ? len[i] : 0;
   for (int d = 32; d > 0; d >>= 1) { const int o = __shfl_xor(v, d); if (o > v) v = o; }
   if ((threadIdx.x & 63) == 0 && v > 0) atomicMax(out, (unsigned long long)v);
+}
+
+// ---- ProcessRead of pairs that lie in two scanned pieces (t4_text_process_pairs) ---------------------------------------------------
+// One pair per wavefront: pair i is record firstA + i of piece A (read 1) and record firstB + i of piece B (read 2), both pieces with
+// status 0, so no read is longer than T4_MAXL and every record has as many qualities as bases. The wave stages the pair in LDS as
+// processPairKernel does -- the text is read once, byte by byte at whatever alignment the lines have -- and runs that kernel's body
+// (processPairStaged). meta[i] = {kind, length of read 1 afterwards, flags, where}: a changed read 1 (flag 16) stands at outR + where
+// with its qualities at outQ + where, where is -1 otherwise. Lane 0 takes the room from *need; a read that would reach beyond outCap is
+// counted and not written (where -1: the host sees *need > outCap and the call is repeated with more room). skip[i] != 0: the pair
+// is not looked at, its kind is -1.
+__global__ __launch_bounds__(64) void textProcessPairKernel(const char *textA, const unsigned *lineA, long long firstA, const char *textB, const unsigned *lineB,
+                                                            long long firstB, long long n, const unsigned char *skip, char *outR, char *outQ,
+                                                            long long outCap, unsigned long long *need, int4 *meta) {
+  __shared__ char s_r1[T4_MAXL + 8], s_q1[T4_MAXL + 8], s_f[T4_MAXL + 8], s_fq[T4_MAXL + 8];
+  __shared__ char s_m[2 * T4_MAXL + 16], s_mq[2 * T4_MAXL + 16];
+  const int lane = laneId();
+  for (long long p = blockIdx.x; p < n; p += gridDim.x) {
+    if (skip && skip[p]) { if (lane == 0) meta[p] = make_int4(-1, 0, 0, -1); continue; }
+    const unsigned *la = lineA + 4 * (firstA + p), *lb = lineB + 4 * (firstB + p);
+    const unsigned seqA = la[1], qualA = la[3], seqB = lb[1], qualB = lb[3];
+    int slen = (int)(la[2] - 1 - seqA), flen = (int)(lb[2] - 1 - seqB);
+    // (what t4_text_scan has checked; held here too, so that no index below leaves the LDS arrays whatever the table says)
+    slen = slen < 0 ? 0 : slen > T4_MAXL ? T4_MAXL : slen;
+    flen = flen < 0 ? 0 : flen > T4_MAXL ? T4_MAXL : flen;
+    for (int i = lane; i < slen; i += 64) { s_r1[i] = textA[seqA + i]; s_q1[i] = textA[qualA + i]; }
+    for (int i = lane; i < flen; i += 64) { s_f[i] = rcChar(textB[seqB + flen - 1 - i]); s_fq[i] = textB[qualB + flen - 1 - i]; }
+    __syncthreads();
+    int kind, outLen, flags;
+    processPairStaged(s_r1, s_q1, s_f, s_fq, s_m, s_mq, slen, flen, true, true, kind, outLen, flags);
+    int where = -1;
+    if (flags & 16) {
+      if (lane == 0) {
+        const unsigned long long at = atomicAdd(need, (unsigned long long)outLen);
+        if (at + (unsigned long long)outLen <= (unsigned long long)outCap && at <= 0x7fffffffull) where = (int)at;
+      }
+      where = __shfl(where, 0);
+      if (where >= 0) for (int j = lane; j < outLen; j += 64) { outR[where + j] = s_m[j]; outQ[where + j] = s_mq[j]; }
+    }
+    if (lane == 0) meta[p] = make_int4(kind, outLen, flags, where);
+    __syncthreads();
+  }
 }
 
 // ---- the candidate test (FastqExtractor.cpp:129-134, 516-519) ----------------------------------------------------------------------

@@ -35,6 +35,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <memory>
 #include <thread>
 #include <string>
 #include <unordered_map>
@@ -43,6 +44,8 @@
 #include "../../include/trust4_hip.h"
 #include "process_read.h"
 #include "seq_reader.h"
+#include "byte_stream.h"
+#include "text_records.h"
 
 extern char **environ;
 
@@ -682,6 +685,7 @@ int main(int argc, char *argv[]) {
   // rank reads the barcode file once ahead of the input loop, and the loop then builds, ProcessReads and counts the 21-mers of the
   // pairs of ITS cells only. Every rank still splits the FASTQ text of the whole sample into records (no record can be found without
   // the ones before it) and numbers every UMI (numbers are in order of first appearance over the whole sample, main.cpp:831-842).
+  // (Under T4_GPU_PARSE=1 the device splits the text, and the rank's host threads touch the records of its own cells only: below.)
   // The 21-mer counts of the whole sample, which the statistics of every read look at, are put together afterwards: counts only
   // ever add up (KmerCount.hpp:64-97), so every rank hands the others the pairs of its table and adds theirs where it holds the k-mer
   // (t4_kmer_count_export / _merge; one all-gather). T4_SHARD_INPUT=0: every rank runs the input phases over the whole sample
@@ -732,7 +736,208 @@ int main(int argc, char *argv[]) {
   }
   std::vector<std::string> barcodeIntToStr;
   std::vector<int> barcodePairCount;   // main.cpp:822-828 (only counted under --contigMinCov)
+  // ---- the device path of the input loop (T4_GPU_PARSE=1, the switch of the stage-0 extractor; opt-in): the two mate files go to the
+  // device piece by piece as bytes. The device finds the records and validates them (t4_text_scan), and runs ProcessRead on the pairs
+  // where they lie (t4_text_process_pairs) -- no host thread splits the text, and nothing is marshalled. The host numbers barcodes
+  // and UMIs (small files, their readers as below), sets a skip byte for every pair that is dropped or another rank's, and builds
+  // the read records of the pairs that are left straight from the piece (text_records.h). It takes text for which "four lines per
+  // record" and SeqReader mean the same; at the first piece that is anything else everything gathered so far is dropped and the
+  // whole input goes through the host loop below, which has not read a byte by then (so the files must be readable twice).
+  const bool wantTextPath = getenv("T4_GPU_PARSE") && atoi(getenv("T4_GPU_PARSE")) == 1;
+  bool textPath = false;
   {
+    auto regular = [](const std::vector<std::string> &files) { for (const std::string &f : files) { struct stat sb; if (stat(f.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return false; } return true; };
+    const char *hostWhy = nullptr;
+    if (!wantTextPath) hostWhy = "T4_GPU_PARSE is not 1";
+    else if (!hasMate || mateReads.files.empty()) hostWhy = "single-end input";
+    else if (reads.files.size() != 1 || mateReads.files.size() != 1) hostWhy = "more than one file per mate";
+    else if (!regular(reads.files) || !regular(mateReads.files)) hostWhy = "a read file that is not a regular file cannot be read twice";
+    else if (!regular(barcodeFile.files) || !regular(umiFile.files)) hostWhy = "a barcode or UMI file that is not a regular file cannot be read twice";
+    if (!hostWhy) {
+      size_t pieceBytes = (size_t)16 << 20;
+#ifdef T4_TEST_KNOBS
+      if (getenv("T4_TEST_TEXT_PIECE")) pieceBytes = (size_t)atol(getenv("T4_TEST_TEXT_PIECE"));   // test builds: small inputs cross piece boundaries
+#endif
+      gpuReady();
+      struct Side {
+        ByteStream in;
+        t4_text *tx = nullptr;
+        std::vector<char> buf;
+        size_t fill = 0;          // bytes of buf in use: what the last piece left over, then fresh bytes
+        bool ended = false;       // the file has no bytes beyond buf[fill)
+        long long recBase = 0;    // records of the file ahead of this piece
+        int64_t info[5] = {0, 0, 0, -1, 0};
+        std::vector<uint32_t> recStart;
+      } side[2];
+      // (readers of their own for the small files: the ones of the host loop stay untouched for a give-back)
+      std::unique_ptr<ThreadedSeqReader> bcIn(new ThreadedSeqReader()), umiIn(new ThreadedSeqReader());
+      bcIn->files = barcodeFile.files; umiIn->files = umiFile.files;
+      for (int sI = 0; sI < 2; ++sI) {
+        if ((rc = t4_text_create(ctx, (int64_t)pieceBytes, &side[sI].tx))) die(ctx, "t4_text_create", rc);
+        side[sI].buf.resize(pieceBytes);
+        side[sI].in.start(sI == 0 ? reads.files[0] : mateReads.files[0], std::max<size_t>(1, std::min<size_t>(pieceBytes / 4, (size_t)4 << 20)));
+      }
+      auto closeText = [&]() { for (int sI = 0; sI < 2; ++sI) { side[sI].in.finish(); t4_text_destroy(side[sI].tx); side[sI].tx = nullptr; } bcIn.reset(); umiIn.reset(); };
+      auto unevenText = [&](const char *what) { fprintf(stderr, "%s\n", what); closeText(); if (initThread.joinable()) initThread.join(); exit(1); };
+      auto now = []() { return std::chrono::steady_clock::now(); };
+      auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
+      double secWait = 0, secScan = 0, secNumber = 0, secPairs = 0, secBuild = 0;
+      int fallStatus = 0, fallSide = 0; long long fallRec = -1;
+      std::vector<uint8_t> skip;
+      std::vector<int> bc, umi;
+      std::vector<int32_t> meta;
+      std::vector<char> outR, outQ;
+      const size_t PP_CHUNK = 1024;
+      for (;;) {
+        auto t0 = now();
+        for (int sI = 0; sI < 2; ++sI) {
+          Side &sd = side[sI];
+          if (!sd.ended) sd.fill += sd.in.take(sd.buf.data() + sd.fill, pieceBytes - sd.fill, &sd.ended);
+          if (sd.in.failed) { fprintf(stderr, "Could not open %s\n", sd.in.path.c_str()); closeText(); if (initThread.joinable()) initThread.join(); exit(EXIT_FAILURE); }
+        }
+        secWait += since(t0); t0 = now();
+        for (int sI = 0; sI < 2 && !fallStatus; ++sI) {
+          Side &sd = side[sI];
+          if ((rc = t4_text_scan(sd.tx, sd.buf.data(), (int64_t)sd.fill, sd.ended ? 1 : 0, sd.info))) die(ctx, "t4_text_scan", rc);
+          if (sd.info[2]) { fallStatus = (int)sd.info[2]; fallRec = sd.recBase + sd.info[3]; fallSide = sI; }
+        }
+        secScan += since(t0);
+        if (fallStatus) break;
+        const int64_t n1 = side[0].info[0], n2 = side[1].info[0], m = std::min(n1, n2);
+        if (m == 0) {
+          if (n1 == 0 && side[0].ended) break;   // every read has been seen (what the mate file has beyond them is not looked at, as on the host path)
+          if (n2 == 0 && side[1].ended) unevenText("The mate-pair read file has fewer reads than the first read file.");
+          fallStatus = 9; fallSide = n1 == 0 ? 0 : 1; fallRec = side[fallSide].recBase;   // a record that does not fit a piece
+          break;
+        }
+        t0 = now();
+        const size_t n = (size_t)m;
+        for (int sI = 0; sI < 2; ++sI) {
+          side[sI].recStart.resize(n + 1);
+          if ((rc = t4_text_records(side[sI].tx, 0, m, side[sI].recStart.data(), nullptr))) die(ctx, "t4_text_records", rc);
+        }
+        secScan += since(t0); t0 = now();
+        // barcodes and UMIs of the m pairs, numbered in order of first appearance; the skip bytes (main.cpp:799-842, as the host loop)
+        bc.assign(n, -1); umi.assign(n, -1); skip.assign(n, 0);
+        if (hasBarcode)
+          for (size_t i = 0; i < n; ++i) {
+            if (!bcIn->next()) unevenText("The barcode file has fewer records than the read file.");
+            const std::string &bs = bcIn->seq;
+            if (bs == "missing_barcode" && !keepMissingBarcode) { skip[i] = 1; continue; }
+            bool isNew = false;
+            const int barcode = barcodeNumbers.number(bs, isNew);
+            if (isNew) barcodeIntToStr.push_back(bs);
+            if (contigMinCov > 0) { if (barcode >= (int)barcodePairCount.size()) barcodePairCount.push_back(1); else ++barcodePairCount[barcode]; }
+            bc[i] = barcode;
+            if (shardInput && (barcode < ownLo || barcode >= ownHi)) skip[i] = 2;
+          }
+        if (hasUmi)
+          for (size_t i = 0; i < n; ++i) {
+            if (!umiIn->next()) unevenText("The UMI file has fewer records than the read file.");
+            if (skip[i] == 1) continue;
+            bool isNew = false;
+            umi[i] = umiNumbers.number(umiIn->seq, isNew);
+          }
+        size_t kept = 0;
+        for (size_t i = 0; i < n; ++i) if (skip[i] != 1) {
+          if (firstReadLen == -1) {
+            TextRecord tr;
+            firstReadLen = cutTextRecord(side[0].buf.data(), side[0].fill, side[0].recStart.data(), i, tr) ? (int)tr.seqLen : 0;
+            if (firstReadLen > 200) { fprintf(stderr, "trust4-hip: long-read mode (first read > 200 bp, main.cpp:1467-1481) is not built.\n"); closeText(); if (initThread.joinable()) initThread.join(); return EXIT_FAILURE; }
+          }
+          ++kept;
+        }
+        const int before = nIn;
+        nIn += (int)(kept * 2);
+        for (int t = before / 100000 + 1; t <= nIn / 100000; ++t) PrintLog("Read in and count kmers for %d reads.", t * 100000);
+        secNumber += since(t0); t0 = now();
+        // ProcessRead of the pairs on the device, where they lie
+        meta.resize(n * 4);
+        const size_t room = (side[0].fill + side[1].fill) / 2;
+        if (outR.size() < room) { outR.resize(room); outQ.resize(room); }
+        int64_t outBytes = 0;
+        if ((rc = t4_text_process_pairs(side[0].tx, side[1].tx, 0, 0, m, skip.data(), meta.data(), outR.data(), outQ.data(), (int64_t)room, &outBytes))) die(ctx, "t4_text_process_pairs", rc);
+        for (size_t i = 0; i < n; ++i) if (!skip[i]) ++ppKinds[meta[i * 4] & 3];
+        secPairs += since(t0); t0 = now();
+        // the read records of the pairs that are left, on the host threads, in input order
+        const size_t nChunks = (n + PP_CHUNK - 1) / PP_CHUNK;
+        std::vector<std::vector<SortRead>> &outs = chunkOuts;
+        if (outs.size() < nChunks) outs.resize(nChunks);
+        std::atomic<bool> badCut(false);
+        parallelFor((long long)nChunks, threadCnt, [&](long long c) {
+          std::vector<SortRead> &out = outs[(size_t)c];
+          const size_t lo = (size_t)c * PP_CHUNK, hi = lo + PP_CHUNK < n ? lo + PP_CHUNK : n;
+          out.clear();
+          out.reserve((hi - lo) * 2 + 2);
+          TextRecord a, b;
+          for (size_t i = lo; i < hi; ++i) {
+            if (skip[i]) continue;
+            const int len = meta[i * 4 + 1], fl = meta[i * 4 + 2], at = meta[i * 4 + 3];
+            if (!cutTextRecord(side[0].buf.data(), side[0].fill, side[0].recStart.data(), i, a) ||
+                !cutTextRecord(side[1].buf.data(), side[1].fill, side[1].recStart.data(), i, b)) { badCut.store(true); continue; }
+            if (fl & 1) {
+              out.emplace_back();
+              SortRead &r1 = out.back();
+              textRecordId(a, reads.stripMateSuffix, r1.id);
+              if (fl & 16) { r1.read.assign(outR.data() + at, (size_t)len); if (fl & 8) r1.qual.assign(outQ.data() + at, (size_t)len); }
+              else { r1.read.assign(a.seq, a.seqLen); r1.qual.assign(a.qual, a.qualLen); }
+              r1.hasQual = (fl & 8) != 0;
+              r1.barcode = bc[i]; r1.umi = umi[i];
+              if (fl & 4) { SortRead w = r1; w.id += ".1"; out.push_back(std::move(w)); }
+            }
+            if (fl & 2) {
+              out.emplace_back();
+              SortRead &r2 = out.back();
+              textRecordId(b, mateReads.stripMateSuffix, r2.id);
+              r2.read.assign(b.seq, b.seqLen); r2.qual.assign(b.qual, b.qualLen);
+              for (char &ch : r2.read) if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T' && ch != 'N') ch = 'N';   // what two reverse complements leave
+              r2.hasQual = true;
+              r2.barcode = bc[i]; r2.umi = umi[i];
+            }
+          }
+        });
+        if (badCut.load()) { fprintf(stderr, "trust4-hip: T4_GPU_PARSE: the record table of a piece does not fit its text\n"); closeText(); return EXIT_FAILURE; }
+        {
+          std::vector<size_t> first(nChunks + 1, sortedReads.size());
+          for (size_t c = 0; c < nChunks; ++c) first[c + 1] = first[c] + outs[c].size();
+          sortedReads.resize(first[nChunks]);
+          parallelFor((long long)nChunks, threadCnt, [&](long long c) {
+            std::vector<SortRead> &v = outs[(size_t)c];
+            for (size_t j = 0; j < v.size(); ++j) sortedReads[first[(size_t)c] + j] = std::move(v[j]);
+            v.clear();
+          });
+        }
+        for (int sI = 0; sI < 2; ++sI) {   // what the piece holds beyond record m goes to the front of the next one
+          Side &sd = side[sI];
+          const size_t used = sd.recStart[n];
+          memmove(sd.buf.data(), sd.buf.data() + used, sd.fill - used);
+          sd.fill -= used; sd.recBase += m;
+        }
+        secBuild += since(t0);
+      }
+      const std::string fallFile = side[fallSide].in.path;
+      closeText();
+      if (!fallStatus) {
+        textPath = true;
+        if (getenv("T4_TIMING")) {
+          PrintLog("path: device text (T4_GPU_PARSE=1, pieces of %zu bytes)", pieceBytes);
+          PrintLog("timing: device text: %.2f s waiting for pieces, %.2f s finding the records, %.2f s numbering, %.2f s ProcessRead on the device, %.2f s building the read records", secWait, secScan, secNumber, secPairs, secBuild);
+        }
+        secProcess = secPairs; secMerge = secBuild;
+      } else {
+        PrintLog("T4_GPU_PARSE: status %d at record %lld of %s; the whole input goes through the host loop", fallStatus, fallRec, fallFile.c_str());
+        hostWhy = "the device path gave the input back";
+        // (everything the loop has gathered goes: the host loop starts from nothing, as without the switch)
+        std::vector<SortRead>().swap(sortedReads);
+        barcodeNumbers = StrNumbering(); umiNumbers = StrNumbering();
+        barcodeIntToStr.clear(); barcodePairCount.clear();
+        firstReadLen = -1; nIn = 0;
+        for (long long &k : ppKinds) k = 0;
+      }
+    }
+    if (hostWhy && getenv("T4_TIMING")) PrintLog("path: host (%s)", hostWhy);
+  }
+  if (!textPath) {
     ThreadedSeqReader::Block bR, bM, bB, bU;
     auto uneven = [&](const char *what) { fprintf(stderr, "%s\n", what); if (processThread.joinable()) processThread.join(); if (initThread.joinable()) initThread.join(); exit(1); };
     while (reads.nextBlock(bR)) {
@@ -807,7 +1012,7 @@ int main(int argc, char *argv[]) {
   flushBlock();
   { const auto tw = std::chrono::steady_clock::now(); if (processThread.joinable()) processThread.join(); secWaitProcess += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count(); }
   if (getenv("T4_TIMING")) PrintLog("timing: input loop %.2f s, of which %.2f s waiting for the ProcessRead of the batch before", std::chrono::duration<double>(std::chrono::steady_clock::now() - tInput0).count(), secWaitProcess);
-  if (gpuProcess) PrintLog("ProcessRead on the device: %lld pairs stay as they are, %lld read-through, %lld merged, %lld with one mate for both", ppKinds[0], ppKinds[1], ppKinds[2], ppKinds[3]);
+  if (gpuProcess || textPath) PrintLog("ProcessRead on the device: %lld pairs stay as they are, %lld read-through, %lld merged, %lld with one mate for both", ppKinds[0], ppKinds[1], ppKinds[2], ppKinds[3]);
   if (gpuProcess && ppBlocksOnHost) PrintLog("ProcessRead: %lld blocks held a mate beyond the device path's length and were processed on the host threads", ppBlocksOnHost);
   if (getenv("T4_TIMING")) PrintLog("timing: input parsed and mates processed (ProcessRead %.2f s on %d threads, merge %.2f s)", secProcess, threadCnt, secMerge);
   const auto tInputEnd = std::chrono::steady_clock::now();
