@@ -304,6 +304,22 @@ int t4_process_pairs(t4_ctx *ctx, int n, const int64_t *off1, const char *r1, co
 int t4_text_process_pairs(t4_text *reads, t4_text *mates, int64_t first_read, int64_t first_mate, int64_t n, const uint8_t *skip,
                           int32_t *meta4, char *out_r, char *out_q, int64_t out_cap, int64_t *out_bytes);
 
+/* The pairs of the last t4_text_process_pairs call as a batch, without a host copy: what the stage-1 driver appends to its read list
+ * for them, in that order -- pairs in input order; of a pair read 1 if flag 1 is set, the same read once more if flag 4 is set (a
+ * merged read counts twice), read 2 if flag 2 is set; a skipped pair gives no row. Rows are packed in T4_READS_KMERS_ONLY coding as
+ * t4_reads_upload_flags packs the same strings: read 1 from its record, or from the changed reads on the device when flag 16 is
+ * set; read 2 from its record with every letter other than A, C, G, T turned into N. with_quals != 0: the batch also carries the
+ * quality bytes of its rows and their offsets (t4_kmer_count_stats_resident). The low-complexity bytes of the batch are 0.
+ * info[0] = rows, info[1] = their bases, info[2] = the longest row, info[3] = 1 when a surviving read 1 holds a letter other than
+ * A, C, G, T, N (it is packed as code 3, as an upload would; the driver then takes its host path).
+ * T4_ERR_ARG unless the last t4_text_process_pairs call with these two handles as `reads` and `mates` succeeded, covered exactly
+ * [first_read, first_read + n) / [first_mate, first_mate + n), and neither handle has scanned a piece since. T4_ERR_UNSUPPORTED
+ * when a row is longer than 384 bases (a merged read may reach the length of both mates); both handles stay usable. n == 0, or no
+ * row at all, gives an empty batch. Scratch belongs to `reads`: made by its first call, reused, freed by t4_text_destroy. The
+ * batch owns its rows and qualities: it outlives the next scan and the handles. */
+int t4_text_pairs_batch(t4_text *reads, t4_text *mates, int64_t first_read, int64_t first_mate, int64_t n, int with_quals,
+                        t4_batch **out, int64_t info[4]);
+
 /* ---- ordered contig builder (host-side commit logic + GPU queries) ----------------------------------
  * t4_assembler owns a mutable set of novel contigs (the reference's `SeqSet seqSet`, main.cpp:642) and exposes
  * the members stage 1 calls on it, with the same arguments and return values:
@@ -473,6 +489,15 @@ int t4_kmer_count_set(t4_kmer_counter *kc, const uint64_t *codes, const int32_t 
  * (the read's length when it is not trimmed, 0 when it is emptied). */
 int t4_kmer_count_stats(t4_kmer_counter *kc, t4_batch *reads, const char *quals, const int64_t *qual_off,
                         int32_t *min_cnt, int32_t *median_cnt, float *avg_cnt, int32_t *new_len);
+/* t4_kmer_count_stats with the qualities and offsets the batch itself carries (t4_text_pairs_batch with with_quals != 0): nothing
+ * is uploaded. use_quals == 0: no trimming (quals == NULL above). T4_ERR_ARG when use_quals != 0 and the batch carries none. */
+int t4_kmer_count_stats_resident(t4_kmer_counter *kc, t4_batch *reads, int use_quals, int32_t *min_cnt, int32_t *median_cnt,
+                                 float *avg_cnt, int32_t *new_len);
+/* Room for `incoming` more distinct k-mers at a load of at most 0.6, for a read set whose size is not known when the counter is
+ * made (pieces of a stream, gzip input): the table is rehashed into a larger one as often as that takes, and the ceiling that
+ * max_kmers of t4_kmer_count_create stood for moves with it (device memory permitting: T4_ERR_HIP otherwise, the table as it was).
+ * A batch of b bases adds fewer than b k-mers. */
+int t4_kmer_count_reserve(t4_kmer_counter *kc, int64_t incoming);
 /* number of distinct k-mers counted so far */
 int64_t t4_kmer_count_distinct(t4_kmer_counter *kc);
 /* The counts of two read sets put together. KmerCount::AddCount (KmerCount.hpp:64-97) only increments, so the table of a union of

@@ -106,7 +106,10 @@ def _load():
         "t4_text_create": (I, [P, L, C.POINTER(P)]), "t4_text_destroy": (None, [P]), "t4_text_scan": (I, [P, P, L, I, P]),
         "t4_text_process_pairs": (I, [P, P, L, L, L, P, P, P, P, L, C.POINTER(L)]),
         "t4_text_batch": (I, [P, L, L, C.POINTER(P)]), "t4_text_records": (I, [P, L, L, P, P]), "t4_candidate_test": (I, [P, P, P, P]),
+        "t4_text_pairs_batch": (I, [P, P, L, L, L, I, C.POINTER(P), P]), "t4_kmer_count_stats_resident": (I, [P, P, I, P, P, P, P]),
+        "t4_kmer_count_reserve": (I, [P, L]),
         # ... and its test aids (csrc/t4_internal.h)
+        "t4_batch_quals": (I, [P, P, L, P, C.POINTER(L)]),
         "t4_batch_read": (I, [P, P, P, P, P, P]), "t4_text_lines": (I, [P, P, L, C.POINTER(L)]), "t4_text_tile_bytes": (I, []),
     }
     for name, (res, args) in sig.items():
@@ -330,6 +333,20 @@ class KmerCounter:
             qb, qo = qbuf.ctypes.data_as(V), qoff.ctypes.data_as(V)
         self.eng.check(self.eng.lib.t4_kmer_count_stats(self.h, batch.h, qb, qo, mn.ctypes.data_as(V), md.ctypes.data_as(V), av.ctypes.data_as(V), ln.ctypes.data_as(V)))
         return mn, md, av, ln
+
+    def stats_resident(self, batch, use_quals=True):
+        """t4_kmer_count_stats_resident: stats() with the qualities the batch itself carries (Text.pairs_batch)"""
+        n = batch.n
+        mn, md, ln = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        av = np.zeros(n, dtype=np.float32)
+        V = C.c_void_p
+        self.eng.check(self.eng.lib.t4_kmer_count_stats_resident(self.h, batch.h, 1 if use_quals else 0, mn.ctypes.data_as(V), md.ctypes.data_as(V), av.ctypes.data_as(V), ln.ctypes.data_as(V)))
+        return mn, md, av, ln
+
+    def reserve(self, incoming):
+        """room for `incoming` more k-mers, beyond what max_kmers stood for if need be (t4_kmer_count_reserve)"""
+        self.eng.check(self.eng.lib.t4_kmer_count_reserve(self.h, C.c_int64(incoming)))
+        return self
 
     def export(self):
         """-> (codes uint64[n], counts int32[n]): the table's pairs, in any order (t4_kmer_count_export)"""
@@ -759,6 +776,16 @@ class Batch:
         self.eng.check(self.eng.lib.t4_batch_read(self.h, dims.ctypes.data_as(V), pk.ctypes.data_as(V), nm.ctypes.data_as(V), ln.ctypes.data_as(V), low.ctypes.data_as(V)))
         return pk, nm, ln, low, int(dims[2])
 
+    def quals(self):
+        """t4_batch_quals (test aid) -> (quality bytes uint8 [nbytes], offsets int64 [n + 1]), or None for a batch that carries none"""
+        nb = C.c_int64(0)
+        self.eng.check(self.eng.lib.t4_batch_quals(self.h, None, 0, None, C.byref(nb)))
+        if nb.value < 0:
+            return None
+        q, off = np.zeros(max(nb.value, 1), dtype=np.uint8), np.zeros(self.n + 1, dtype=np.int64)
+        self.eng.check(self.eng.lib.t4_batch_quals(self.h, q.ctypes.data_as(C.c_void_p), len(q), off.ctypes.data_as(C.c_void_p), C.byref(nb)))
+        return q[:nb.value], off
+
     def close(self):
         if getattr(self, "h", None):
             self.eng.lib.t4_batch_destroy(self.h)
@@ -841,6 +868,13 @@ class Text:
                 rd = self.data[a:a + ln].decode("latin-1"); ql = self.data[b:b + ln]
             res.append((kind, rd, ql, fl & 15))
         return res
+
+    def pairs_batch(self, mates, first=0, first_mate=0, n=None, with_quals=True):
+        """t4_text_pairs_batch: the pairs of the last process_pairs call as a Batch -> (batch, (rows, bases, longest row, other-letter flag))"""
+        n = self.nrec - first if n is None else n
+        h, info = C.c_void_p(), np.zeros(4, dtype=np.int64)
+        self.eng.check(self.eng.lib.t4_text_pairs_batch(self.h, mates.h, first, first_mate, n, 1 if with_quals else 0, C.byref(h), info.ctypes.data_as(C.c_void_p)))
+        return Batch.from_handle(self.eng, h, int(info[0])), tuple(int(x) for x in info)
 
     def lines(self):
         """t4_text_lines (test aid) -> the line table of the piece last scanned: uint32 [lines + 1] (empty piece: [0])"""

@@ -263,6 +263,7 @@ struct t4_ctx {
   const int32_t *aqLastTicks = nullptr; int aqLastN = 0;   // per-read wall-clock ticks (10 ns) of the last AddRead query call (in the pinned header blob)
   double aqLastMs = 0;
   AqCall aq;
+  uint64_t textScans = 0;   // t4_text_scan calls of the ctx's handles so far: every scan has a number of its own (t4_text::scanId)
   uint64_t syncEpoch = 1;   // bumped whenever the ctx's stream has been waited for: work queued before that is done (t4_index_apply_delta's staging buffer)
   // testing aids of the AddRead query path, read from the environment once per ctx (a query round is a few hundred microseconds; a
   // dozen getenv calls in it are not nothing)
@@ -333,6 +334,9 @@ struct t4_batch {
   DevBuf<unsigned> dPk, dNm;
   DevBuf<int> dLen, dBarcode;
   DevBuf<unsigned char> dLow;   // low-complexity bytes (batches of t4_text_batch; null otherwise: no read counts as low)
+  DevBuf<char> dQual;           // batches of t4_text_pairs_batch made with qualities: the rows' quality bytes, qualBytes of them ...
+  DevBuf<long long> dQoff;      // ... and where each row's begin (n + 1 offsets); null otherwise
+  long long qualBytes = 0;
   T4BatchView view;
 };
 
@@ -355,7 +359,18 @@ struct t4_text {
   DevBuf<unsigned long long> dPairNeed;       // bytes the changed reads take
   PinnedBuf<unsigned long long> pairNeedHost;
   int64_t pairCap = 0;
+  // the last t4_text_process_pairs call with this handle as `reads`: whether it succeeded, what it covered and which scans it looked at
+  bool pairOk = false;
+  const t4_text *pairMates = nullptr;
+  int64_t pairFirst[2] = {0, 0}, pairN = 0;
+  uint64_t pairScan[2] = {0, 0};
+  // t4_text_pairs_batch with this handle as `reads`: made by the first call, reused
+  DevBuf<uint2> dRowAt;                       // per record of the piece: rows and bases ahead of the pair in its workgroup
+  DevBuf<unsigned long long> dRowBlock;       // per workgroup of T4_TEXT_THREADS pairs: rows, then bases
+  DevBuf<unsigned long long> dRowInfo;        // T4_PAIRROWS_WORDS words
+  PinnedBuf<unsigned long long> rowInfoHost;
   // the piece last scanned
+  uint64_t scanId = 0;                        // which scan of the ctx (t4_ctx::textScans) it was: 0 none
   int status = -1;                            // -1: none
   int64_t nbytes = 0, lines = 0, nrec = 0, recBytes = 0, badRec = -1;
   int longest = 0;
@@ -1543,6 +1558,26 @@ int t4_kmer_count_merge(t4_kmer_counter *kc, const uint64_t *codes, const int32_
   return T4_OK;
 }
 
+namespace {
+// kmerStatsKernel over the n > 0 rows of b and its four result arrays to the host; quals / qoff: device pointers, or null for no trimming
+int kmerStatsRun(t4_kmer_counter *kc, t4_batch *b, const char *quals, const long long *qoff, int32_t *min_cnt, int32_t *median_cnt, float *avg_cnt, int32_t *new_len) {
+  t4_ctx *c = kc->ctx;
+  const long long n = b->n;
+  int r;
+  DevBuf<int> dMin, dMed, dLen; DevBuf<float> dAvg;
+  if ((r = dMin.alloc(c, (size_t)n)) || (r = dMed.alloc(c, (size_t)n)) || (r = dLen.alloc(c, (size_t)n)) || (r = dAvg.alloc(c, (size_t)n))) return r;
+  const int grid = (int)(n < (long long)c->cus * 32 ? n : (long long)c->cus * 32);
+  launch(t4k::kmerStatsKernel, grid, 64, c->stream, b->view, kc->tb, quals, qoff, dMin, dMed, dAvg, dLen);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(min_cnt, dMin, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(median_cnt, dMed, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(avg_cnt, dAvg, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(new_len, dLen, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return T4_OK;
+}
+}  // namespace
+
 int t4_kmer_count_stats(t4_kmer_counter *kc, t4_batch *b, const char *quals, const int64_t *qual_off,
                         int32_t *min_cnt, int32_t *median_cnt, float *avg_cnt, int32_t *new_len) {
   if (!kc || !b || !min_cnt || !median_cnt || !avg_cnt || !new_len || (quals && !qual_off)) return T4_ERR_ARG;
@@ -1554,7 +1589,6 @@ int t4_kmer_count_stats(t4_kmer_counter *kc, t4_batch *b, const char *quals, con
   (void)hipSetDevice(c->device);
   int r;
   DevBuf<char> dQ; DevBuf<long long> dOff;
-  DevBuf<int> dMin, dMed, dLen; DevBuf<float> dAvg;
   if (quals) {
     std::vector<int> lens((size_t)n);
     HIPCHK(c, hipMemcpy(lens.data(), b->dLen, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
@@ -1565,16 +1599,25 @@ int t4_kmer_count_stats(t4_kmer_counter *kc, t4_batch *b, const char *quals, con
     if (qn) HIPCHK(c, hipMemcpy(dQ, quals, qn, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(dOff, qual_off, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice));
   }
-  if ((r = dMin.alloc(c, (size_t)n)) || (r = dMed.alloc(c, (size_t)n)) || (r = dLen.alloc(c, (size_t)n)) || (r = dAvg.alloc(c, (size_t)n))) return r;
-  const int grid = (int)(n < (long long)c->cus * 32 ? n : (long long)c->cus * 32);
-  launch(t4k::kmerStatsKernel, grid, 64, c->stream, b->view, kc->tb, (const char *)dQ, (const long long *)dOff, dMin, dMed, dAvg, dLen);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(min_cnt, dMin, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(median_cnt, dMed, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(avg_cnt, dAvg, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(new_len, dLen, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return T4_OK;
+  return kmerStatsRun(kc, b, dQ, dOff, min_cnt, median_cnt, avg_cnt, new_len);
+}
+
+int t4_kmer_count_stats_resident(t4_kmer_counter *kc, t4_batch *b, int use_quals, int32_t *min_cnt, int32_t *median_cnt, float *avg_cnt, int32_t *new_len) {
+  if (!kc || !b || !min_cnt || !median_cnt || !avg_cnt || !new_len) return T4_ERR_ARG;
+  t4_ctx *c = kc->ctx;
+  if (b->ctx != c) return fail(c, T4_ERR_ARG, "batch belongs to another ctx");
+  if (use_quals && !b->dQoff.p) return fail(c, T4_ERR_ARG, "t4_kmer_count_stats_resident: the batch carries no qualities");
+  const long long n = b->n;
+  if (n == 0) return T4_OK;
+  if (kc->tb.perBarcode && !b->dBarcode) return fail(c, T4_ERR_ARG, "t4_kmer_count_stats_resident: per-barcode counts need a batch uploaded with barcodes");
+  (void)hipSetDevice(c->device);
+  return kmerStatsRun(kc, b, use_quals ? b->dQual.p : nullptr, use_quals ? b->dQoff.p : nullptr, min_cnt, median_cnt, avg_cnt, new_len);
+}
+
+int t4_kmer_count_reserve(t4_kmer_counter *kc, int64_t incoming) {
+  if (!kc || incoming < 0) return T4_ERR_ARG;
+  (void)hipSetDevice(kc->ctx->device);
+  return incoming ? kmerEnsureRoom(kc, (unsigned long long)incoming, true) : T4_OK;
 }
 
 int64_t t4_kmer_count_distinct(t4_kmer_counter *kc) {
@@ -1630,6 +1673,7 @@ int t4_text_scan(t4_text *tx, const char *text, int64_t nbytes, int final_piece,
   if (!tx || !info) return T4_ERR_ARG;
   t4_ctx *c = tx->ctx;
   tx->status = -1; tx->nbytes = tx->lines = tx->nrec = tx->recBytes = 0; tx->badRec = -1; tx->longest = 0;
+  tx->scanId = ++c->textScans; tx->pairOk = false;
   if (nbytes < 0 || nbytes > tx->cap || (nbytes > 0 && !text)) return fail(c, T4_ERR_ARG, "t4_text_scan: %lld bytes for a handle made for %lld", (long long)nbytes, (long long)tx->cap);
   (void)hipSetDevice(c->device);
   unsigned long long *h = tx->infoHost;
@@ -1724,7 +1768,13 @@ int t4_text_process_pairs(t4_text *reads, t4_text *mates, int64_t first_read, in
   if (!reads || !mates || !out_bytes) return T4_ERR_ARG;
   t4_ctx *c = reads->ctx;
   *out_bytes = 0;
+  reads->pairOk = false;
   if (mates->ctx != c) return fail(c, T4_ERR_ARG, "t4_text_process_pairs: the two pieces belong to different contexts");
+  auto covered = [&]() {   // what t4_text_pairs_batch asks for
+    reads->pairOk = true; reads->pairMates = mates; reads->pairFirst[0] = first_read; reads->pairFirst[1] = first_mate; reads->pairN = n;
+    reads->pairScan[0] = reads->scanId; reads->pairScan[1] = mates->scanId;
+    return T4_OK;
+  };
   const t4_text *side[2] = {reads, mates};
   const int64_t firsts[2] = {first_read, first_mate};
   for (int k = 0; k < 2; ++k) {
@@ -1735,7 +1785,7 @@ int t4_text_process_pairs(t4_text *reads, t4_text *mates, int64_t first_read, in
       return fail(c, T4_ERR_ARG, "t4_text_process_pairs: records [%lld, %lld) of a piece of the %s of %lld", (long long)firsts[k], (long long)(firsts[k] + n), what, (long long)side[k]->nrec);
   }
   if (out_cap < 0 || (n > 0 && !meta4) || (out_cap > 0 && (!out_r || !out_q))) return fail(c, T4_ERR_ARG, "t4_text_process_pairs: no room for the result");
-  if (n == 0) return T4_OK;
+  if (n == 0) return covered();
   (void)hipSetDevice(c->device);
   t4_text *tx = reads;
   int r;
@@ -1767,6 +1817,64 @@ int t4_text_process_pairs(t4_text *reads, t4_text *mates, int64_t first_read, in
     HIPCHK(c, hipMemcpyAsync(out_q, tx->dPairQ, (size_t)need, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  return covered();
+}
+
+int t4_text_pairs_batch(t4_text *reads, t4_text *mates, int64_t first_read, int64_t first_mate, int64_t n, int with_quals, t4_batch **out, int64_t info[4]) {
+  if (!reads || !mates || !out || !info) return T4_ERR_ARG;
+  *out = nullptr;
+  info[0] = info[1] = info[2] = info[3] = 0;
+  t4_ctx *c = reads->ctx;
+  t4_text *tx = reads;
+  if (!tx->pairOk || tx->pairMates != mates) return fail(c, T4_ERR_ARG, "t4_text_pairs_batch: the last t4_text_process_pairs call on these two handles did not succeed (or there was none)");
+  if (tx->pairScan[0] != reads->scanId || tx->pairScan[1] != mates->scanId) return fail(c, T4_ERR_ARG, "t4_text_pairs_batch: a piece has been scanned again since t4_text_process_pairs");
+  if (tx->pairFirst[0] != first_read || tx->pairFirst[1] != first_mate || tx->pairN != n)
+    return fail(c, T4_ERR_ARG, "t4_text_pairs_batch: pairs [%lld, %lld) / [%lld, %lld), t4_text_process_pairs covered [%lld, %lld) / [%lld, %lld)", (long long)first_read, (long long)(first_read + n),
+                (long long)first_mate, (long long)(first_mate + n), (long long)tx->pairFirst[0], (long long)(tx->pairFirst[0] + tx->pairN), (long long)tx->pairFirst[1], (long long)(tx->pairFirst[1] + tx->pairN));
+  (void)hipSetDevice(c->device);
+  int r;
+  long long rows = 0, bases = 0;
+  int longest = 0;
+  unsigned long long *h = nullptr;
+  const size_t recs = (size_t)(tx->cap / 4) + 1, maxBlocks = (recs + T4_TEXT_THREADS - 1) / T4_TEXT_THREADS;   // workgroups of the row scan: rows, then bases in dRowBlock
+  if (n > 0) {
+    if ((!tx->dRowAt.p && (r = tx->dRowAt.alloc(c, recs))) || (!tx->dRowBlock.p && (r = tx->dRowBlock.alloc(c, 2 * maxBlocks))) ||
+        (!tx->dRowInfo.p && (r = tx->dRowInfo.alloc(c, T4_PAIRROWS_WORDS))) || (!tx->rowInfoHost.p && (r = tx->rowInfoHost.alloc(c, T4_PAIRROWS_WORDS, hipHostMallocDefault)))) return r;
+    h = tx->rowInfoHost;
+    const int blocks = (int)((n + T4_TEXT_THREADS - 1) / T4_TEXT_THREADS);
+    HIPCHK(c, hipMemsetAsync(tx->dRowInfo, 0, sizeof(unsigned long long) * T4_PAIRROWS_WORDS, c->stream));
+    launch(t4k::textPairRowsKernel, blocks, T4_TEXT_THREADS, c->stream, tx->dPairMeta, mates->dLineStart, (long long)first_mate, (long long)n, tx->dRowAt,
+           tx->dRowBlock, tx->dRowBlock + maxBlocks, tx->dRowInfo);
+    launch(t4k::textPairScanKernel, 1, T4_TEXT_THREADS, c->stream, tx->dRowBlock, tx->dRowBlock + maxBlocks, blocks, tx->dRowInfo);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h, tx->dRowInfo, sizeof(unsigned long long) * T4_PAIRROWS_WORDS, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rows = (long long)h[T4_PAIRROWS_ROWS]; bases = (long long)h[T4_PAIRROWS_BASES]; longest = (int)h[T4_PAIRROWS_LONGEST];
+    info[0] = rows; info[1] = bases; info[2] = longest;
+    if (longest > T4_MAXL) return fail(c, T4_ERR_UNSUPPORTED, "t4_text_pairs_batch: a read of %d bases (a merged read may reach the length of both mates), a batch takes %d", longest, T4_MAXL);
+  }
+  std::unique_ptr<t4_batch> b(new t4_batch());
+  b->ctx = c; b->n = rows; b->maxLen = longest;
+  b->wpk = std::max(1, (longest + 15) / 16); b->wnm = std::max(1, (longest + 31) / 32);
+  if ((r = b->dPk.alloc(c, (size_t)rows * b->wpk + 4)) || (r = b->dNm.alloc(c, (size_t)rows * b->wnm + 4)) || (r = b->dLen.alloc(c, (size_t)rows)) || (r = b->dLow.alloc(c, (size_t)rows))) return r;
+  if (with_quals) {
+    if ((r = b->dQual.alloc(c, (size_t)bases + 16)) || (r = b->dQoff.alloc(c, (size_t)rows + 1))) return r;
+    b->qualBytes = bases;
+    if (rows == 0) HIPCHK(c, hipMemsetAsync(b->dQoff, 0, sizeof(long long), c->stream));
+  }
+  if (rows > 0) {
+    HIPCHK(c, hipMemsetAsync(b->dLow, 0, (size_t)rows, c->stream));
+    launch(t4k::textPairPackKernel, (int)((n * 32 + T4_TEXT_THREADS - 1) / T4_TEXT_THREADS), T4_TEXT_THREADS, c->stream, reads->dText, reads->dLineStart, (long long)first_read,
+           mates->dText, mates->dLineStart, (long long)first_mate, (long long)n, tx->dPairMeta, tx->dPairR, tx->dPairQ, (long long)tx->pairCap, tx->dRowAt, tx->dRowBlock,
+           tx->dRowBlock + maxBlocks, b->dPk, b->dNm, b->wpk, b->wnm, b->dLen, b->dQual, b->dQoff, tx->dRowInfo);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h + T4_PAIRROWS_OTHER, tx->dRowInfo + T4_PAIRROWS_OTHER, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    info[3] = h[T4_PAIRROWS_OTHER] ? 1 : 0;
+  }
+  b->view.pk = b->dPk; b->view.nm = b->dNm; b->view.len = b->dLen; b->view.barcode = nullptr;
+  b->view.wpk = b->wpk; b->view.wnm = b->wnm; b->view.n = rows;
+  *out = b.release();
   return T4_OK;
 }
 
@@ -1795,6 +1903,20 @@ int t4_batch_read(t4_batch *b, int32_t dims[3], uint32_t *pk, uint32_t *nm, int3
   if (nm) HIPCHK(c, hipMemcpy(nm, b->dNm, sizeof(uint32_t) * n * b->wnm, hipMemcpyDeviceToHost));
   if (len) HIPCHK(c, hipMemcpy(len, b->dLen, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
   if (low) { if (b->dLow.p) HIPCHK(c, hipMemcpy(low, b->dLow, n, hipMemcpyDeviceToHost)); else memset(low, 0, n); }
+  return T4_OK;
+}
+
+// (tests) the qualities a batch carries: *nbytes = how many (-1: none, nothing else is written), quals (room for cap >= *nbytes, or null), qual_off (n + 1 offsets, or null)
+int t4_batch_quals(t4_batch *b, char *quals, int64_t cap, int64_t *qual_off, int64_t *nbytes) {
+  if (!b || !nbytes) return T4_ERR_ARG;
+  t4_ctx *c = b->ctx;
+  *nbytes = b->dQoff.p ? (int64_t)b->qualBytes : -1;
+  if (!b->dQoff.p) return T4_OK;
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (quals && cap < b->qualBytes) return fail(c, T4_ERR_ARG, "t4_batch_quals: room for %lld bytes, the batch has %lld", (long long)cap, b->qualBytes);
+  if (quals && b->qualBytes > 0) HIPCHK(c, hipMemcpy(quals, b->dQual, (size_t)b->qualBytes, hipMemcpyDeviceToHost));
+  if (qual_off) HIPCHK(c, hipMemcpy(qual_off, b->dQoff, sizeof(long long) * ((size_t)b->n + 1), hipMemcpyDeviceToHost));
   return T4_OK;
 }
 

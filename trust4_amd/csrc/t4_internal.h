@@ -111,6 +111,9 @@ int t4_cellstore_read_image(t4_cellstore *cs, int slot, void *buf, size_t cap, s
 int t4_batch_read(t4_batch *b, int32_t dims[3], uint32_t *pk, uint32_t *nm, int32_t *len, uint8_t *low);
 int t4_text_lines(t4_text *tx, uint32_t *line_start, int64_t cap, int64_t *lines);
 int t4_text_tile_bytes(void);
+// ... and the qualities a batch of t4_text_pairs_batch carries: *nbytes = how many bytes (-1: the batch carries none, and nothing
+// else is written), quals (room for cap >= *nbytes bytes; or null), qual_off (n + 1 offsets; or null)
+int t4_batch_quals(t4_batch *b, char *quals, int64_t cap, int64_t *qual_off, int64_t *nbytes);
 
 // t4_add_query with variable-size results (a read may overlap thousands of contigs that share a gene segment): counts[i]
 // records of read i start at index base[i] of ov / ext / ext_ret, which point into pinned memory of the ctx that stays

@@ -1,6 +1,6 @@
 // trust4_amd/csrc/t4_text.h -- FASTQ text on the device: line table, record validation, 2-bit packing, the low-complexity rule, the
-// combine step of the stage-0 candidate test and stage 1's ProcessRead on pairs that lie in two pieces (included by t4_api.hip
-// behind t4_kernels.h, namespace t4k).
+// combine step of the stage-0 candidate test, stage 1's ProcessRead on pairs that lie in two pieces and those pairs afterwards as the
+// rows of a batch with their qualities (included by t4_api.hip behind t4_kernels.h, namespace t4k).
 //
 // A piece of text of nbytes bytes lies in device memory padded to a whole number of tiles (T4_TEXT_TILE bytes, one workgroup of
 // T4_TEXT_THREADS lanes with one 16-byte load each), so every load is in bounds; bytes at or beyond nbytes never count. Line j of the
@@ -224,6 +224,152 @@ __global__ __launch_bounds__(64) void textProcessPairKernel(const char *textA, c
     if (lane == 0) meta[p] = make_int4(kind, outLen, flags, where);
     __syncthreads();
   }
+}
+
+// ---- the pairs after ProcessRead as the rows of a batch (t4_text_pairs_batch) --------------------------------------------------------
+// What the driver appends to its read list for pair i (meta[i] of the last t4_text_process_pairs call): read 1 if flag 1 is set, the
+// same read once more if flag 4 is set too (a merged read counts twice), read 2 if flag 2 is set; a skipped pair (kind -1, flags 0)
+// gives nothing. Rows stand in that order, pairs in input order; the qualities of row r stand at qoff[r] of one byte buffer.
+// Three kernels: the rows and bases of every pair with their exclusive scan inside a workgroup of T4_TEXT_THREADS pairs
+// (textPairRowsKernel), the scan over the workgroups' sums (textPairScanKernel, one workgroup: the two levels of textCountKernel /
+// textScanKernel), and the packing (textPairPackKernel). Words they leave for the host:
+#define T4_PAIRROWS_ROWS 0      // rows of the batch
+#define T4_PAIRROWS_BASES 1     // bases (= quality bytes) of all rows
+#define T4_PAIRROWS_LONGEST 2   // longest row
+#define T4_PAIRROWS_OTHER 3     // 1: a surviving read 1 holds a letter other than A, C, G, T, N (it is packed as code 3)
+#define T4_PAIRROWS_WORDS 4
+
+// exclusive scan of v over the workgroup's lanes, the sum of all of them in total; s: one word per wave
+__device__ __forceinline__ unsigned textBlockExclusive(unsigned v, unsigned *s, unsigned &total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned incl = v;
+  for (int d = 1; d < 64; d <<= 1) { const unsigned up = __shfl_up(incl, (unsigned)d); if (lane >= d) incl += up; }
+  if (lane == 63) s[wave] = incl;
+  __syncthreads();
+  unsigned before = incl - v;
+  total = 0;
+  for (int w = 0; w < T4_TEXT_THREADS / 64; ++w) { if (w < wave) before += s[w]; total += s[w]; }
+  __syncthreads();
+  return before;
+}
+
+// length of read 2 of a pair as the line table of piece B has it, held to what t4_text_scan has checked
+__device__ __forceinline__ int textMateLen(const unsigned *lb) {
+  const long long len = (long long)lb[2] - 1 - (long long)lb[1];
+  return len < 0 ? 0 : len > T4_MAXL ? T4_MAXL : (int)len;
+}
+
+// One pair per lane. rowAt[p] = {rows, bases} of the pairs ahead of p in its workgroup; blockRows / blockBases[workgroup] = its sums.
+__global__ __launch_bounds__(T4_TEXT_THREADS) void textPairRowsKernel(const int4 *meta, const unsigned *lineB, long long firstB, long long n, uint2 *rowAt,
+                                                                      unsigned long long *blockRows, unsigned long long *blockBases, unsigned long long *info) {
+  __shared__ unsigned s_w[T4_TEXT_THREADS / 64];
+  const long long p = (long long)blockIdx.x * T4_TEXT_THREADS + threadIdx.x;
+  unsigned rows = 0, bases = 0;
+  int longest = 0;
+  if (p < n) {
+    const int4 m = meta[p];
+    const int len1 = m.y < 0 ? 0 : m.y, len2 = textMateLen(lineB + 4 * (firstB + p));
+    const unsigned rows1 = (m.z & 1) ? ((m.z & 4) ? 2u : 1u) : 0u, rows2 = (m.z & 2) ? 1u : 0u;
+    rows = rows1 + rows2;
+    bases = rows1 * (unsigned)len1 + rows2 * (unsigned)len2;   // (a merged read has at most 2 T4_MAXL bases: no carry)
+    longest = rows1 ? len1 : 0;
+    if (rows2 && len2 > longest) longest = len2;
+  }
+  unsigned allRows, allBases;
+  const unsigned rowsBefore = textBlockExclusive(rows, s_w, allRows), basesBefore = textBlockExclusive(bases, s_w, allBases);
+  if (p < n) { uint2 at; at.x = rowsBefore; at.y = basesBefore; rowAt[p] = at; }
+  if (threadIdx.x == 0) { blockRows[blockIdx.x] = allRows; blockBases[blockIdx.x] = allBases; }
+  for (int d = 32; d > 0; d >>= 1) { const int o = __shfl_xor(longest, d); if (o > longest) longest = o; }
+  if ((threadIdx.x & 63) == 0 && longest > 0) atomicMax(&info[T4_PAIRROWS_LONGEST], (unsigned long long)longest);
+}
+
+// (one workgroup) the workgroups' sums become their exclusive scans (64-bit: the offsets kmerStatsKernel reads), info receives the totals
+__global__ __launch_bounds__(T4_TEXT_THREADS) void textPairScanKernel(unsigned long long *blockRows, unsigned long long *blockBases, int nblocks, unsigned long long *info) {
+  __shared__ unsigned long long s_rows[T4_TEXT_THREADS], s_bases[T4_TEXT_THREADS];
+  const int per = (nblocks + T4_TEXT_THREADS - 1) / T4_TEXT_THREADS;
+  const int lo = (int)threadIdx.x * per, hi = lo + per < nblocks ? lo + per : nblocks;
+  unsigned long long rows = 0, bases = 0;
+  for (int t = lo; t < hi; ++t) { rows += blockRows[t]; bases += blockBases[t]; }
+  s_rows[threadIdx.x] = rows; s_bases[threadIdx.x] = bases;
+  __syncthreads();
+  unsigned long long rowsBefore = 0, basesBefore = 0;
+  for (int t = 0; t < (int)threadIdx.x; ++t) { rowsBefore += s_rows[t]; basesBefore += s_bases[t]; }
+  for (int t = lo; t < hi; ++t) {
+    const unsigned long long r = blockRows[t], b = blockBases[t];
+    blockRows[t] = rowsBefore; blockBases[t] = basesBefore;
+    rowsBefore += r; basesBefore += b;
+  }
+  if (threadIdx.x == T4_TEXT_THREADS - 1) { info[T4_PAIRROWS_ROWS] = rowsBefore; info[T4_PAIRROWS_BASES] = basesBefore; }
+}
+
+// One half-wavefront per pair, as textRecordKernel<true> packs: lane l packs bases 16 l .. 16 l + 15 of a row (no row is longer than
+// T4_MAXL: the host has looked at info[T4_PAIRROWS_LONGEST]), lanes 2 m and 2 m + 1 combine their N masks through a shuffle. Read 1
+// comes from its record, or from pairR + where when flag 16 is set (qualities: pairQ + where); read 2 from its record with every
+// letter other than A, C, G, T turned into N. Every byte is read once, at whatever alignment the lines have. qual / qoff null: a
+// batch without qualities. A half-wavefront without a row goes through the wave-wide steps with an empty one.
+__global__ __launch_bounds__(T4_TEXT_THREADS) void textPairPackKernel(const char *textA, const unsigned *lineA, long long firstA, const char *textB, const unsigned *lineB,
+                                                                      long long firstB, long long n, const int4 *meta, const char *pairR, const char *pairQ,
+                                                                      long long pairCap, const uint2 *rowAt, const unsigned long long *blockRows,
+                                                                      const unsigned long long *blockBases, unsigned *pk, unsigned *nm, int wpk, int wnm, int *len,
+                                                                      char *qual, long long *qoff, unsigned long long *info) {
+  const int l = threadIdx.x & 31;
+  const long long p = ((long long)blockIdx.x * T4_TEXT_THREADS + threadIdx.x) >> 5;
+  const bool live = p < n;
+  int4 m; m.x = -1; m.y = 0; m.z = 0; m.w = -1;
+  long long row = 0, qat = 0;
+  unsigned seqA = 0, qualA = 0, seqB = 0, qualB = 0;
+  int len2 = 0;
+  if (live) {
+    m = meta[p];
+    const uint2 at = rowAt[p];
+    row = (long long)blockRows[p / T4_TEXT_THREADS] + at.x; qat = (long long)blockBases[p / T4_TEXT_THREADS] + at.y;
+    const unsigned *la = lineA + 4 * (firstA + p), *lb = lineB + 4 * (firstB + p);
+    seqA = la[1]; qualA = la[3]; seqB = lb[1]; qualB = lb[3];
+    len2 = textMateLen(lb);
+  }
+  const int fl = m.z;
+  int otherIn1 = 0;
+  for (int side = 0; side < 2; ++side) {
+    const bool use = (fl & (side ? 2 : 1)) != 0;
+    const char *src = textB + seqB, *qsrc = textB + qualB;
+    int ln = len2;
+    if (side == 0) {
+      ln = m.y;
+      src = textA + seqA; qsrc = textA + qualA;
+      if (fl & 16) {
+        // (a call that succeeded has written every changed read inside the buffers; held here too, so that no load leaves them)
+        if (m.w < 0 || (long long)m.w + ln > pairCap) ln = 0;
+        else { src = pairR + m.w; qsrc = pairQ + m.w; }
+      }
+    }
+    if (!use || ln < 0 || ln > T4_MAXL) ln = 0;
+    unsigned word = 0, mask = 0;
+    for (int k = 0; k < 16; ++k) {
+      const int j = 16 * l + k;
+      if (j >= ln) break;
+      const char ch = src[j];
+      unsigned v = 3;
+      if (ch == 'A') v = 0;
+      else if (ch == 'C') v = 1;
+      else if (ch == 'G') v = 2;
+      else if (ch == 'T') v = 3;
+      else if (ch == 'N' || side == 1) { v = 0; mask |= 1u << k; }
+      else otherIn1 = 1;
+      word |= v << (2 * k);
+    }
+    const unsigned hi = __shfl_down(mask, 1u);
+    if (!use) continue;   // (uniform over the half-wavefront; nothing wave-wide below)
+    const int copies = side == 0 && (fl & 4) ? 2 : 1;
+    if (qual) for (int j = l; j < ln; j += 32) { const char q = qsrc[j]; qual[qat + j] = q; if (copies == 2) qual[qat + ln + j] = q; }
+    for (int c = 0; c < copies; ++c) {
+      if (l < wpk) pk[row * wpk + l] = word;
+      if (!(l & 1) && (l >> 1) < wnm) nm[row * wnm + (l >> 1)] = mask | hi << 16;
+      if (l == 0) { len[row] = ln; if (qoff) qoff[row] = qat; }
+      ++row; qat += ln;
+    }
+  }
+  if (otherIn1) info[T4_PAIRROWS_OTHER] = 1ull;
+  if (live && p == n - 1 && l == 0 && qoff) qoff[info[T4_PAIRROWS_ROWS]] = (long long)info[T4_PAIRROWS_BASES];
 }
 
 // ---- the candidate test (FastqExtractor.cpp:129-134, 516-519) ----------------------------------------------------------------------

@@ -745,6 +745,35 @@ int main(int argc, char *argv[]) {
   // whole input goes through the host loop below, which has not read a byte by then (so the files must be readable twice).
   const bool wantTextPath = getenv("T4_GPU_PARSE") && atoi(getenv("T4_GPU_PARSE")) == 1;
   bool textPath = false;
+  // T4_TEXT_COUNTS=1 (opt-in, looked at on the device text path only): the 21-mers are counted piece by piece from the text the device
+  // holds -- the pairs of a piece after ProcessRead become a batch with their qualities where they lie (t4_text_pairs_batch), no base and
+  // no quality is uploaded a second time. The batches are kept for the statistics pass under the rule of the uploaded chunks below
+  // (keepBatches), and when no reads are dealt to other ranks after the counts. A -c file or T4_GPU_KMERCOUNT=0 leave it off; a piece
+  // whose reads the device counters do not take (a read 1 with a letter other than ACGTN, a merged read beyond 384 bases) or a device
+  // allocation that fails drops the counter and the batches, and the counts are taken further down as without the switch.
+  const bool wantTextCounts = getenv("T4_TEXT_COUNTS") && atoi(getenv("T4_TEXT_COUNTS")) == 1;
+  struct TextCounts {
+    bool on = false;
+    std::string offWhy;                       // why the switch does nothing in this run
+    t4_kmer_counter *kc = nullptr;
+    std::vector<t4_batch *> kept;             // in input order; kept[i] holds keptRows[i] reads of sortedReads, one behind the other
+    std::vector<size_t> keptRows;
+    bool keep = false;
+    long long batches = 0, batchesKept = 0;
+    double sec = 0;
+    void dropKept() { for (t4_batch *b : kept) t4_batch_destroy(b); kept.clear(); keptRows.clear(); keep = false; }
+    void drop(const char *why) { dropKept(); if (kc) t4_kmer_count_destroy(kc); kc = nullptr; on = false; offWhy = why; batches = batchesKept = 0; }
+  } textCounts;
+  if (wantTextCounts) {
+    if (!kmerCountFile.empty()) textCounts.offWhy = "a -c file";
+    else if (getenv("T4_GPU_KMERCOUNT") && atoi(getenv("T4_GPU_KMERCOUNT")) == 0) textCounts.offWhy = "T4_GPU_KMERCOUNT=0";
+    else {
+      textCounts.on = true;
+      // (reads that go to other ranks after the counts -- --cellShard without the dealt-out input -- would sit in the batches)
+      const bool dealtLater = shardCount > 1 && !lateShard && (!rcclIdPath.empty() || !gatherDir.empty()) && !shardInput;
+      textCounts.keep = contigMinCov <= 0 && !dealtLater;
+    }
+  }
   {
     auto regular = [](const std::vector<std::string> &files) { for (const std::string &f : files) { struct stat sb; if (stat(f.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return false; } return true; };
     const char *hostWhy = nullptr;
@@ -864,6 +893,7 @@ int main(int argc, char *argv[]) {
         std::vector<std::vector<SortRead>> &outs = chunkOuts;
         if (outs.size() < nChunks) outs.resize(nChunks);
         std::atomic<bool> badCut(false);
+        double secCountPiece = 0;   // T4_TEXT_COUNTS=1: the seconds of this piece's count, which are not the record building's
         parallelFor((long long)nChunks, threadCnt, [&](long long c) {
           std::vector<SortRead> &out = outs[(size_t)c];
           const size_t lo = (size_t)c * PP_CHUNK, hi = lo + PP_CHUNK < n ? lo + PP_CHUNK : n;
@@ -906,6 +936,44 @@ int main(int argc, char *argv[]) {
             for (size_t j = 0; j < v.size(); ++j) sortedReads[first[(size_t)c] + j] = std::move(v[j]);
             v.clear();
           });
+          if (textCounts.on) {   // T4_TEXT_COUNTS=1: the reads just appended, counted where the device holds them
+            const auto tc0 = now();
+            const size_t appended = first[nChunks] - first[0];
+            int64_t binfo[4] = {0, 0, 0, 0};
+            t4_batch *tb = nullptr;
+            const char *why = nullptr;
+            std::string whyText;
+            auto soft = [&](const char *call, const char *unsupported) {   // what sends the run back to the uploaded reads; anything else is an error of the run
+              // (T4_ERR_HIP is every HIP error: only memory that could not be had leaves the device fit for the path without the switch)
+              const char *msg = rc == T4_ERR_HIP ? t4_last_error(ctx) : "";
+              const bool noMemory = strstr(msg, "hipMalloc") || strstr(msg, "hipHostMalloc") || strstr(msg, "no device memory");
+              if (rc == T4_ERR_HIP && noMemory) { whyText = std::string("a device allocation failed: ") + msg; why = whyText.c_str(); }
+              else if (rc == T4_ERR_UNSUPPORTED) why = unsupported;
+              else if (rc) die(ctx, call, rc);
+            };
+            rc = t4_text_pairs_batch(side[0].tx, side[1].tx, 0, 0, m, trimLevel != 0 ? 1 : 0, &tb, binfo);
+            soft("t4_text_pairs_batch", "a merged read beyond 384 bases");
+            if (!why && binfo[3]) why = "a letter other than ACGTN in a read 1";
+            if (!why && (size_t)binfo[0] != appended) {
+              fprintf(stderr, "trust4-hip: T4_TEXT_COUNTS: the device made %lld reads of a piece, the host %zu\n", (long long)binfo[0], appended);
+              closeText(); if (initThread.joinable()) initThread.join(); return EXIT_FAILURE;
+            }
+            if (!why && !textCounts.kc) { rc = t4_kmer_count_create(ctx, 21, 1ll << 21, 0, &textCounts.kc); soft("t4_kmer_count_create", "the count table"); }
+            // (the size of the read set is not known while the pieces stream: room for this piece's k-mers, fewer than its bases)
+            if (!why) { rc = t4_kmer_count_reserve(textCounts.kc, binfo[1]); soft("t4_kmer_count_reserve", "the count table is full"); }
+            if (!why) { rc = t4_kmer_count_add(textCounts.kc, tb); soft("t4_kmer_count_add", "the count table is full"); }
+            if (why) {
+              if (tb) t4_batch_destroy(tb);
+              textCounts.drop(why);
+            } else {
+              ++textCounts.batches;
+              if (textCounts.keep && sortedReads.size() > ((size_t)16 << 20)) textCounts.dropKept();   // (60 B per read on the device, and their qualities)
+              if (textCounts.keep) { textCounts.kept.push_back(tb); textCounts.keptRows.push_back(appended); }
+              else t4_batch_destroy(tb);
+            }
+            secCountPiece = since(tc0);
+            textCounts.sec += secCountPiece;
+          }
         }
         for (int sI = 0; sI < 2; ++sI) {   // what the piece holds beyond record m goes to the front of the next one
           Side &sd = side[sI];
@@ -913,7 +981,7 @@ int main(int argc, char *argv[]) {
           memmove(sd.buf.data(), sd.buf.data() + used, sd.fill - used);
           sd.fill -= used; sd.recBase += m;
         }
-        secBuild += since(t0);
+        secBuild += since(t0) - secCountPiece;
       }
       const std::string fallFile = side[fallSide].in.path;
       closeText();
@@ -924,7 +992,12 @@ int main(int argc, char *argv[]) {
           PrintLog("timing: device text: %.2f s waiting for pieces, %.2f s finding the records, %.2f s numbering, %.2f s ProcessRead on the device, %.2f s building the read records", secWait, secScan, secNumber, secPairs, secBuild);
         }
         secProcess = secPairs; secMerge = secBuild;
+        if (textCounts.on && !textCounts.kc) textCounts.drop("the input holds no pair");
+        textCounts.batchesKept = (long long)textCounts.kept.size();
+        if (textCounts.on && getenv("T4_TIMING"))
+          PrintLog("timing: 21-mers counted from the device's reads (T4_TEXT_COUNTS=1): %lld batches in %.2f s of the input loop, %lld kept for the statistics", textCounts.batches, textCounts.sec, textCounts.batchesKept);
       } else {
+        if (textCounts.on) textCounts.drop("the input went through the host loop");   // (the counter and the batches go with everything else)
         PrintLog("T4_GPU_PARSE: status %d at record %lld of %s; the whole input goes through the host loop", fallStatus, fallRec, fallFile.c_str());
         hostWhy = "the device path gave the input back";
         // (everything the loop has gathered goes: the host loop starts from nothing, as without the switch)
@@ -936,7 +1009,9 @@ int main(int argc, char *argv[]) {
       }
     }
     if (hostWhy && getenv("T4_TIMING")) PrintLog("path: host (%s)", hostWhy);
+    if (hostWhy && textCounts.on) textCounts.drop("the input went through the host loop");
   }
+  if (wantTextCounts && !textCounts.on) PrintLog("T4_TEXT_COUNTS: the 21-mers are counted from the reads of the host's list as without the switch (%s)", textCounts.offWhy.c_str());
   if (!textPath) {
     ThreadedSeqReader::Block bR, bM, bB, bU;
     auto uneven = [&](const char *what) { fprintf(stderr, "%s\n", what); if (processThread.joinable()) processThread.join(); if (initThread.joinable()) initThread.join(); exit(1); };
@@ -1051,7 +1126,12 @@ int main(int argc, char *argv[]) {
   // Default since round 3 (1 M barcoded pairs: 23.9 -> 21.2 s, profiles/r03l_*): on the device whenever the input is what the device
   // path takes; T4_GPU_KMERCOUNT=0 keeps the host threads, =1 insists (and says why it cannot).
   bool wantGpuKc = false, insistGpuKc = false;
-  if (readCnt > 0) {
+  if (textCounts.on) {   // counted piece by piece in the input loop: every read has qualities (FASTQ text), none is beyond 384 bases or holds another letter
+    gpuKc = textCounts.kc; textCounts.kc = nullptr;
+    gpuKmerCounts = true; gpuQual = trimLevel != 0;
+    if (!textCounts.keep) textCounts.dropKept();
+    if (readCnt <= 0) { t4_kmer_count_destroy(gpuKc); gpuKc = nullptr; gpuKmerCounts = false; gpuQual = false; textCounts.dropKept(); }   // (nothing was counted)
+  } else if (readCnt > 0) {
     const char *ev = getenv("T4_GPU_KMERCOUNT");
     if (ev) { wantGpuKc = atoi(ev) != 0; insistGpuKc = wantGpuKc; }
     else {
@@ -1105,7 +1185,7 @@ int main(int argc, char *argv[]) {
       gpuKmerCounts = false; gpuQual = false;
       if (kmerCountFile.empty()) kmerCount.addCountAll((long long)sortedReads.size(), threadCnt, [&](long long i) -> const std::string & { return sortedReads[(size_t)i].read; });
     }
-  } else if (kmerCountFile.empty())
+  } else if (kmerCountFile.empty() && !textCounts.on)
   kmerCount.addCountAll((long long)sortedReads.size(), threadCnt, [&](long long i) -> const std::string & { return sortedReads[(size_t)i].read; });
   if (getenv("T4_TIMING")) PrintLog("timing: 21-mers counted%s (%.2f s since the input ended)", gpuKc ? " (on the device)" : "", std::chrono::duration<double>(std::chrono::steady_clock::now() - tInputEnd).count());
   gpuReady();
@@ -1197,14 +1277,45 @@ int main(int argc, char *argv[]) {
     readCnt = (int)sortedReads.size();
     for (t4_batch *kb : countedBatches) t4_batch_destroy(kb);   // (the chunks of the count pass held every rank's reads)
     countedBatches.clear();
+    textCounts.dropKept();
     PrintLog("Cells %d-%d of %d are this rank's (%d of %lld reads).", bLo, bHi, (int)nb, readCnt, total);
   }
   // ---- count statistics + quality trimming (main.cpp:980-1061)
   if (gpuKc) {
     std::string &bases = scratchBases; std::string quals; std::vector<int64_t> &off = scratchOff;
     std::vector<int32_t> mn, md, nl; std::vector<float> av;
+    auto takeStats = [&](size_t lo, size_t n) {
+      parallelFor((long long)n, threadCnt, [&](long long ii) {
+        const size_t i = (size_t)ii;
+        SortRead &r = sortedReads[lo + i];
+        r.minCnt = mn[i]; r.medianCnt = md[i]; r.avgCnt = av[i];
+        if ((size_t)nl[i] < r.read.size()) r.read.resize((size_t)nl[i]);
+        r.qual.clear(); r.qual.shrink_to_fit(); r.hasQual = false;
+        if (r.read.empty()) r.dead = true;
+      });
+    };
+    // T4_TEXT_COUNTS=1 with its batches kept: they hold the reads of the list in its order, with their qualities -- nothing is uploaded
+    const bool resident = !textCounts.kept.empty();
+    if (resident) {
+      size_t lo = 0;
+      for (size_t bi = 0; bi < textCounts.kept.size(); ++bi) {
+        const size_t n = textCounts.keptRows[bi];
+        if (lo + n > sortedReads.size()) break;
+        mn.resize(n); md.resize(n); nl.resize(n); av.resize(n);
+        if ((rc = t4_kmer_count_stats_resident(gpuKc, textCounts.kept[bi], gpuQual ? 1 : 0, mn.data(), md.data(), av.data(), nl.data()))) die(ctx, "t4_kmer_count_stats_resident", rc);
+        t4_batch_destroy(textCounts.kept[bi]); textCounts.kept[bi] = nullptr;
+        takeStats(lo, n);
+        lo += n;
+      }
+      if (lo != sortedReads.size() || textCounts.kept.back()) {
+        fprintf(stderr, "trust4-hip: T4_TEXT_COUNTS: the kept batches hold %zu reads or more, the list %zu\n", lo, sortedReads.size());
+        if (initThread.joinable()) initThread.join();
+        return EXIT_FAILURE;
+      }
+      textCounts.kept.clear(); textCounts.keptRows.clear();
+    }
     const bool reuse = !countedBatches.empty();
-    for (size_t lo = 0, ci = 0; lo < sortedReads.size(); lo += KC_CHUNK, ++ci) {
+    for (size_t lo = 0, ci = 0; !resident && lo < sortedReads.size(); lo += KC_CHUNK, ++ci) {
       const size_t hi = lo + KC_CHUNK < sortedReads.size() ? lo + KC_CHUNK : sortedReads.size(), n = hi - lo;
       t4_batch *b = reuse ? countedBatches[ci] : uploadChunk(lo, hi, bases, off);
       if (gpuQual && reuse) {   // (the offsets of the qualities: where the bases of the chunk stood)
@@ -1218,14 +1329,7 @@ int main(int argc, char *argv[]) {
       mn.resize(n); md.resize(n); nl.resize(n); av.resize(n);
       if ((rc = t4_kmer_count_stats(gpuKc, b, gpuQual ? quals.data() : nullptr, gpuQual ? off.data() : nullptr, mn.data(), md.data(), av.data(), nl.data()))) die(ctx, "t4_kmer_count_stats", rc);
       t4_batch_destroy(b);
-      parallelFor((long long)n, threadCnt, [&](long long ii) {
-        const size_t i = (size_t)ii;
-        SortRead &r = sortedReads[lo + i];
-        r.minCnt = mn[i]; r.medianCnt = md[i]; r.avgCnt = av[i];
-        if ((size_t)nl[i] < r.read.size()) r.read.resize((size_t)nl[i]);
-        r.qual.clear(); r.qual.shrink_to_fit(); r.hasQual = false;
-        if (r.read.empty()) r.dead = true;
-      });
+      takeStats(lo, n);
     }
     countedBatches.clear();   // (every kept batch was destroyed with its chunk above)
     t4_kmer_count_destroy(gpuKc);
@@ -2206,6 +2310,7 @@ int main(int argc, char *argv[]) {
       fprintf(fp, "\"chain\": {\"rounds\": %.0f, \"restricted_only_rounds\": %.0f, \"round_kernel_ms_p05\": %.4f, \"round_kernel_ms_p50\": %.4f, \"round_wall_ms_p05\": %.4f, \"round_wall_ms_p50\": %.4f, "
                   "\"whole_queries\": %.0f, \"restricted_queries\": %.0f, \"candidate_records\": %.0f, \"restricted_merged_by_replay\": %.0f}, ",
               cs[0], cs[1], cs[2], cs[3], cs[4], cs[5], cs[6], cs[7], cs[8], cs[9]);
+      fprintf(fp, "\"text_counts\": {\"on\": %d, \"batches\": %lld, \"kept\": %lld}, ", textCounts.on ? 1 : 0, textCounts.batches, textCounts.batchesKept);
       fprintf(fp, "\"contigs\": %d, \"assembled_reads\": %d}\n", t4_assembler_size(seqSet), (int)assembledReadIdx.size());
       fclose(fp);
     }
