@@ -472,8 +472,11 @@ int t4_cellset_indexed_stats(const t4_cellset *cs, int64_t *out, int n);
  * it full makes t4_kmer_count_add fail with T4_ERR_UNSUPPORTED). the stage-1 driver calls this under T4_GPU_KMERCOUNT=1 and counts on host threads otherwise. */
 typedef struct t4_kmer_counter t4_kmer_counter;
 /* per_barcode != 0: one KmerCount per barcode in the same table -- the reference's `KmerCount barcodeKmerCount(21, 23)` that is
- * filled, read and cleared barcode after barcode (main.cpp:1126-1160): the read's barcode (t4_reads_upload; at most 2^20 - 2) is
- * part of the key, so reads only see the counts of their own barcode. Takes k <= 21. */
+ * filled, read and cleared barcode after barcode (main.cpp:1126-1160): the read's barcode (t4_reads_upload) is part of the key,
+ * so reads only see the counts of their own barcode. Takes k <= 21, and barcodes -1 (none) .. T4_KMER_COUNT_MAX_BARCODE: barcode + 1
+ * takes the 22 bits above the 42 of a 21-mer. t4_kmer_count_add / _stats / _stats_resident refuse a batch that holds another
+ * (T4_ERR_UNSUPPORTED): it would share its keys with some other barcode's. */
+#define T4_KMER_COUNT_MAX_BARCODE 4194302   /* 2^22 - 2 */
 int t4_kmer_count_create(t4_ctx *ctx, int k, int64_t max_kmers, int per_barcode, t4_kmer_counter **out);
 void t4_kmer_count_destroy(t4_kmer_counter *kc);
 /* AddCount of every read of the batch (reads shorter than k add nothing). */

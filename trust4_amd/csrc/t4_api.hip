@@ -333,6 +333,7 @@ struct t4_batch {
   int wpk = 0, wnm = 0, maxLen = 0;
   DevBuf<unsigned> dPk, dNm;
   DevBuf<int> dLen, dBarcode;
+  int minBarcode = -1, maxBarcode = -1;   // of dBarcode, from the host array it was uploaded from (per-barcode k-mer counts: kmerBarcodesFit)
   DevBuf<unsigned char> dLow;   // low-complexity bytes (batches of t4_text_batch; null otherwise: no read counts as low)
   DevBuf<char> dQual;           // batches of t4_text_pairs_batch made with qualities: the rows' quality bytes, qualBytes of them ...
   DevBuf<long long> dQoff;      // ... and where each row's begin (n + 1 offsets); null otherwise
@@ -1063,6 +1064,7 @@ int t4_reads_upload_flags(t4_ctx *c, const char *bases, const int64_t *offsets, 
   if (barcode) {
     if ((r = b->dBarcode.alloc(c, (size_t)n))) return r;
     if (n > 0) HIPCHK(c, hipMemcpy(b->dBarcode, barcode, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    for (int64_t i = 0; i < n; ++i) { if (barcode[i] < b->minBarcode) b->minBarcode = barcode[i]; if (barcode[i] > b->maxBarcode) b->maxBarcode = barcode[i]; }
   }
   b->view.pk = b->dPk; b->view.nm = b->dNm; b->view.len = b->dLen; b->view.barcode = b->dBarcode;
   b->view.wpk = b->wpk; b->view.wnm = b->wnm; b->view.n = n;
@@ -1383,6 +1385,16 @@ int kmerTableAlloc(t4_ctx *c, unsigned long long slots, T4KmerTable &tb, DevBuf<
   tb.keys = keys; tb.cnt = cnt; tb.mask = slots - 1;
   return T4_OK;
 }
+// A per-barcode counter keys a k-mer as code | (barcode + 1) << 42 (kmerAddKernel, kmerStatsKernel): barcode + 1 has the 22 bits
+// 42..63, and the key is stored as key + 1, so barcodes -1 (none) .. T4_KMER_COUNT_MAX_BARCODE keep apart. One beyond would fold
+// onto another's keys, silently: such a batch is refused. (The extremes were taken on the host when the batch got its barcodes.)
+int kmerBarcodesFit(t4_kmer_counter *kc, const t4_batch *b, const char *who) {
+  if (!kc->tb.perBarcode || !b->dBarcode) return T4_OK;
+  if (b->maxBarcode > T4_KMER_COUNT_MAX_BARCODE || b->minBarcode < -1)
+    return fail(kc->ctx, T4_ERR_UNSUPPORTED, "%s: barcode %d in the batch; a per-barcode counter keys barcodes -1..%d (22 bits of the 64-bit key)",
+                who, b->maxBarcode > T4_KMER_COUNT_MAX_BARCODE ? b->maxBarcode : b->minBarcode, T4_KMER_COUNT_MAX_BARCODE);
+  return T4_OK;
+}
 // Room for `incoming` more k-mers at a load of at most 0.6: the table is rehashed on the device into one four times as large as
 // often as that takes (never beyond the size the caller's max_kmers stands for: then the old behaviour -- a full table fails).
 // raiseMax: the incoming k-mers are another read set's (t4_kmer_count_merge without only_present), which the caller's max_kmers at
@@ -1451,6 +1463,7 @@ int t4_kmer_count_add(t4_kmer_counter *kc, t4_batch *b) {
   (void)hipSetDevice(c->device);
   const long long n = b->n;
   if (kc->tb.perBarcode && !b->dBarcode) return fail(c, T4_ERR_ARG, "t4_kmer_count_add: per-barcode counts need a batch uploaded with barcodes");
+  if (int fit = kmerBarcodesFit(kc, b, "t4_kmer_count_add")) return fit;
   // in slices of reads whose k-mers (every one new, at worst) leave the table under a load of 0.6; between slices the table grows
   const long long perRead = b->maxLen >= kc->tb.k ? (long long)(b->maxLen - kc->tb.k + 1) : 1;
   for (long long lo = 0; lo < n;) {
@@ -1586,6 +1599,7 @@ int t4_kmer_count_stats(t4_kmer_counter *kc, t4_batch *b, const char *quals, con
   const long long n = b->n;
   if (n == 0) return T4_OK;
   if (kc->tb.perBarcode && !b->dBarcode) return fail(c, T4_ERR_ARG, "t4_kmer_count_stats: per-barcode counts need a batch uploaded with barcodes");
+  if (int fit = kmerBarcodesFit(kc, b, "t4_kmer_count_stats")) return fit;
   (void)hipSetDevice(c->device);
   int r;
   DevBuf<char> dQ; DevBuf<long long> dOff;
@@ -1610,6 +1624,7 @@ int t4_kmer_count_stats_resident(t4_kmer_counter *kc, t4_batch *b, int use_quals
   const long long n = b->n;
   if (n == 0) return T4_OK;
   if (kc->tb.perBarcode && !b->dBarcode) return fail(c, T4_ERR_ARG, "t4_kmer_count_stats_resident: per-barcode counts need a batch uploaded with barcodes");
+  if (int fit = kmerBarcodesFit(kc, b, "t4_kmer_count_stats_resident")) return fit;
   (void)hipSetDevice(c->device);
   return kmerStatsRun(kc, b, use_quals ? b->dQual.p : nullptr, use_quals ? b->dQoff.p : nullptr, min_cnt, median_cnt, avg_cnt, new_len);
 }

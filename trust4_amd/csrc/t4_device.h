@@ -169,7 +169,7 @@ struct T4KmerTable {
   unsigned *cnt;
   unsigned long long mask;   // slots - 1 (slots is a power of two)
   int k;
-  int perBarcode;            // 1: the read's barcode is part of the key (bits 42..62; k <= 21) -- one KmerCount per barcode
+  int perBarcode;            // 1: the read's barcode is part of the key (barcode + 1 in bits 42..63, so barcodes -1..2^22 - 2; k <= 21) -- one KmerCount per barcode
   int *overflow;             // set when an insert found the table full
   unsigned long long *used;  // occupied slots (one atomic per wavefront pass): the host grows the table before it fills (t4_kmer_count_add)
 };

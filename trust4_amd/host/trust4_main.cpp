@@ -1477,7 +1477,14 @@ int main(int argc, char *argv[]) {
       groups.push_back({i, j});
       i = j;
     }
-    if (gpuKmerCounts) {   // one device table for all barcodes, the barcode being part of the key (t4_kmer_count_create, per_barcode)
+    // barcodes are numbered in order of appearance and a device table keys -1..T4_KMER_COUNT_MAX_BARCODE: a run with more of them counts
+    // on the host (t4_kmer_count_add would refuse its batches)
+    int maxBarcode = -1;
+    for (const SortRead &r : sortedReads) if (r.barcode > maxBarcode) maxBarcode = r.barcode;
+    const bool barcodesFit = maxBarcode <= T4_KMER_COUNT_MAX_BARCODE;
+    if (gpuKmerCounts && !barcodesFit)
+      PrintLog("Barcode-wise kmer count on the host threads: barcode %d is beyond the %d that the device table keys.", maxBarcode, T4_KMER_COUNT_MAX_BARCODE);
+    if (gpuKmerCounts && barcodesFit) {   // one device table for all barcodes, the barcode being part of the key (t4_kmer_count_create, per_barcode)
       long long kmers = 0;
       for (const SortRead &r : sortedReads) if ((int)r.read.size() >= 21) kmers += (long long)r.read.size() - 20;
       t4_kmer_counter *bkc = nullptr;
